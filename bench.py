@@ -7,8 +7,8 @@ substitutions, 0.05% N.
 `value` is weak-scaled: every rank runs the same per-GPU job at every N, so
 the driver's 1 -> N ratio compares like with like.  The default job is
 BASELINE configs[1]'s: k=28 m=10 x=3 B=2048, 1 GB of FASTA per GPU from a
-100 Mbp virtual genome (--workload picks another).  Beside it the line carries
-`configs2_per_gpu`: configs[2]'s per-GPU load, k=28 m=10 x=3 B=8192, 6.25 GB
+100 Mbp virtual genome (--workload picks another).  With --full the line carries
+`configs2_per_gpu` beside it: configs[2]'s per-GPU load, k=28 m=10 x=3 B=8192, 6.25 GB
 per GPU from a 3 Gbp virtual genome (at N = 8: the 50 GB job), also at every N.
 
 One step = one job over the rank's shard (SparkBinKmerCounter.executeJob,
@@ -25,10 +25,19 @@ fused kernel mapping every landed tile meanwhile, and with N > 1 every landed
 piece exchanged while the next one is copied) and ends with the counts on the
 device.  `device_resident_value` is the same job with the FASTA already in HBM;
 the roofline of the fused encode+signature kernel comes from that leg (HIP
-events around its one launch, on the stream it runs on).  That leg runs at
-N = 1 and <= 2 GB per GPU unless --device-leg asks for it.
+events around its one launch, on the stream it runs on).  That leg runs with
+--full, at N = 1 and <= 2 GB per GPU unless --device-leg asks for it.
 
-Usage:  python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run does only what `value` needs: set up, warm up, time the K steps,
+write --dump-outputs, print the line.  --full adds the other legs to the same
+line: `device_resident_*` and `roofline`, `configs2_per_gpu` and `cpu_baseline`
+(each with its own switch, below).
+
+--dump-outputs DIR writes what the last timed step left on the device (rank 0's
+counts) as float64 DIR/<name>.npy: every bin's size, the job's totals, and the
+sorted (key, count) entries of a fixed, seeded sample of bins (dump_outputs).
+
+Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
           N > 1 without a launcher: bench.py starts N worker processes itself (one per GPU,
           RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 in their environment) before any
           GPU call, and fails if fewer than N GPUs are visible; --dry-run prints that plan.
@@ -197,6 +206,52 @@ class Rank:
         self.host = self.dev_in = None
 
 
+DUMP_SAMPLE_BINS = 8  # bins whose entries --dump-outputs writes
+DUMP_MAX_BYTES = 48 << 20  # of sampled entries (the whole directory stays under 64 MB)
+
+
+def dump_outputs(kc, out_dir: str) -> None:
+    """--dump-outputs: the counts the last timed step left on the device, as a caller reads them
+    (bin_sizes / get_bin / stats), in float64 .npy files (every value below 2^53 is exact):
+      bin_sizes.npy     distinct k-mers of every bin
+      totals.npy        [k-mers counted, distinct k-mers]
+      sample_bins.npy   the sampled bins: the first DUMP_SAMPLE_BINS of a permutation of the bins
+                        seeded with SEED (fewer if their entries would pass DUMP_MAX_BYTES)
+      sample_offsets.npy  entries of sample_bins[i] are rows offsets[i]:offsets[i+1] of the next two
+      sample_keys.npy   [n, 2 or 4]: the keys' 32-bit halves, most significant first
+      sample_counts.npy [n]
+    Each bin's entries are sorted by key, so that a hash count's table order does not show."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    sizes = kc.bin_sizes()
+    st = kc.stats()
+    kw = 2 if kc.k > 32 else 1
+    bins, offsets, keys_out, counts_out, used = [], [0], [], [], 0
+    for b in np.random.default_rng(SEED).permutation(len(sizes))[:DUMP_SAMPLE_BINS].tolist():
+        used += int(sizes[b]) * (2 * kw + 1) * 8
+        if used > DUMP_MAX_BYTES:
+            break
+        keys, counts = kc.get_bin(b)
+        keys = keys.reshape(-1, kw)
+        order = np.lexsort(tuple(keys[:, w] for w in range(kw - 1, -1, -1)))
+        keys, counts = keys[order], counts[order]
+        halves = np.empty((len(keys), 2 * kw), dtype=np.float64)
+        halves[:, 0::2] = keys >> np.uint64(32)
+        halves[:, 1::2] = keys & np.uint64(0xFFFFFFFF)
+        bins.append(b)
+        offsets.append(offsets[-1] + len(keys))
+        keys_out.append(halves)
+        counts_out.append(counts.astype(np.float64))
+    np.save(os.path.join(out_dir, "bin_sizes.npy"), sizes.astype(np.float64))
+    np.save(os.path.join(out_dir, "totals.npy"), np.array([st["kmers"], st["distinct"]], dtype=np.float64))
+    np.save(os.path.join(out_dir, "sample_bins.npy"), np.array(bins, dtype=np.float64))
+    np.save(os.path.join(out_dir, "sample_offsets.npy"), np.array(offsets, dtype=np.float64))
+    np.save(os.path.join(out_dir, "sample_keys.npy"),
+            np.concatenate(keys_out) if keys_out else np.empty((0, 2 * kw), dtype=np.float64))
+    np.save(os.path.join(out_dir, "sample_counts.npy"),
+            np.concatenate(counts_out) if counts_out else np.empty(0, dtype=np.float64))
+
+
 def exchange_figures(st: dict, world: int) -> dict:
     """Per-rank exchange figures from the context's stats (fk_stats.xch_*)."""
     out = {"steps": st["xch_steps"], "bytes_sent": st["xch_bytes_sent"], "bytes_received": st["xch_bytes_received"],
@@ -347,9 +402,10 @@ def timed(topo: Topology, ranks: list, step_name: str, steps: int, warmup: int):
     return topo.max_over_ranks(time.perf_counter() - t0), per
 
 
-def run_leg(args, topo: Topology, wl: str, nbytes: int, device_leg: bool) -> dict:
+def run_leg(args, topo: Topology, wl: str, nbytes: int, device_leg: bool, dump_dir: str = "") -> dict:
     """One workload: the headline leg (pinned-host FASTA -> counts on the device) and, if asked, the
-    HBM-resident leg with the encode+signature kernel's roofline.  Collective over the ranks."""
+    HBM-resident leg with the encode+signature kernel's roofline.  Collective over the ranks.
+    dump_dir: rank 0 writes the headline leg's last counts there (dump_outputs)."""
     ranks = make_ranks(topo, wl, nbytes, args.use_ht, device_leg)
     elapsed, host_stats = timed(topo, ranks, "step_host", args.steps, args.warmup)
     res = {"wl": wl, "elapsed": elapsed, "hs": host_stats[-1][0], "fasta_bytes": ranks[0].fasta_bytes,
@@ -365,6 +421,8 @@ def run_leg(args, topo: Topology, wl: str, nbytes: int, device_leg: bool) -> dic
     host_sizes = [r.kc.bin_sizes() for r in ranks]
     for i, s in enumerate(host_sizes):
         assert int(s.sum()) == host_stats[-1][i]["distinct"] > 0
+    if dump_dir and topo.rank == 0:
+        dump_outputs(ranks[0].kc, dump_dir)
     if device_leg:
         dev_elapsed, dev_stats = timed(topo, ranks, "step_device", args.steps, args.warmup)
         for r, s in zip(ranks, host_sizes):  # size-independent self-check: both legs counted the same shard
@@ -488,6 +546,13 @@ def main() -> None:
                          "starts the N ranks itself; under torchrun it must equal WORLD_SIZE")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside `value`: the HBM-resident leg with the roofline, configs[2]'s "
+                         "per-GPU load and the CPU baseline (each as its own switch below says); off: the "
+                         "headline leg alone")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write rank 0's counts of the last step as DIR/<name>.npy "
+                         "(float64: every bin's size, the totals, a seeded sample of bins' entries)")
     ap.add_argument("--bytes-per-gpu", type=int, default=0, help="FASTA bytes per GPU (0: the workload's)")
     ap.add_argument("--cpu-sample-bytes", type=int, default=160_000_000)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -510,6 +575,10 @@ def main() -> None:
     ap.add_argument("--dry-run", action="store_true",
                     help="with --gpus N > 1: print the ranks' launch plan as JSON and exit (no GPU use)")
     args = ap.parse_args()
+    if not args.full and (args.device_leg or args.c3_leg == "on"):
+        ap.error("--device-leg and --c3-leg on ask for legs of the --full run: add --full")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus is not None and args.gpus > 1 and not args.rehearse_local:
@@ -529,14 +598,15 @@ def main() -> None:
     nbytes = args.bytes_per_gpu or WORKLOADS[wl][6]
     # the roofline leg is the N = 1 line's, at its 1 GB; a 6.25 GB shard (configs[2] / [3] per GPU)
     # would hold both legs' buffers on its GPU at once (k = 55: ~57 GB per k-mer array)
-    device_leg = not args.no_device_leg and (args.device_leg or (topo.n_ranks == 1 and nbytes <= 2_000_000_000))
-    c3_leg = args.c3_leg == "on" or (args.c3_leg == "auto" and wl != "c3" and not topo.local)
+    device_leg = args.full and not args.no_device_leg and (
+        args.device_leg or (topo.n_ranks == 1 and nbytes <= 2_000_000_000))
+    c3_leg = args.full and (args.c3_leg == "on" or (args.c3_leg == "auto" and wl != "c3" and not topo.local))
     numa = pin_to_gpu_numa(topo.local_rank) if topo.distributed else None
     torch.cuda.set_device(0 if topo.local else topo.local_rank)
     if topo.distributed:
         dist.init_process_group("gloo")  # bootstrap + host barriers; the records move over RCCL in the library
 
-    res = run_leg(args, topo, wl, nbytes, device_leg)
+    res = run_leg(args, topo, wl, nbytes, device_leg, args.dump_outputs)
     res3 = run_leg(args, topo, "c3", WORKLOADS["c3"][6], False) if c3_leg else None
 
     if topo.rank == 0:
@@ -582,7 +652,7 @@ def main() -> None:
             out["configs2_per_gpu"] = leg_line(args, topo, res3)
         if topo.distributed:
             out["numa_node_rank0"] = numa  # the node rank 0's CPUs were restricted to (None: left alone)
-        if topo.n_ranks == 1 and not args.no_cpu_baseline and wl == "c2":
+        if args.full and topo.n_ranks == 1 and not args.no_cpu_baseline and wl == "c2":
             out["cpu_baseline"] = cpu_baseline(args.cpu_sample_bytes, k, m, B, read_len, genome)
         print(json.dumps(out), flush=True)
     if topo.distributed:

@@ -9,5 +9,5 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout
     || { tail -40 $O/cp_tests.log; exit 1; }
 tail -2 $O/cp_tests.log
 bash scripts/ab_env.sh FASTKMER_COMPACT "0 1" || exit 1
-cd /tmp && TMPDIR=/tmp timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$O/cp_prof -o run \
-    -- python3 $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 2 --no-cpu-baseline > $GRAFT_REPO_ROOT/$O/cp_prof.log 2>&1 || exit 1
+R=$(pwd); cd /tmp && TMPDIR=/tmp timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/cp_prof -o run \
+    -- python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > $R/$O/cp_prof.log 2>&1 || exit 1

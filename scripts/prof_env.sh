@@ -6,5 +6,5 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out
 VAR=$1; VALS=$2
 for v in $VALS; do
   export $VAR=$v
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/pe_$v -o run -- python3 $R/bench.py --steps 5 --warmup 1 --no-cpu-baseline > $O/pe_$v.json 2> $O/pe_$v.err || exit 1
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/pe_$v -o run -- python3 $R/bench.py --full --steps 5 --warmup 1 --no-cpu-baseline > $O/pe_$v.json 2> $O/pe_$v.err || exit 1
 done

@@ -13,5 +13,5 @@ timeout -k 10 600 python -u -m pytest tests/test_gpu_pieces.py tests/test_gpu_pa
 tail -2 $O/x2_tests.log
 bash scripts/ab_env.sh FASTKMER_X2_L2 "0 512 256 128" || exit 1
 BENCH_ARGS="--workload c4" bash scripts/ab_env.sh FASTKMER_X2_L2 "0 512" || exit 1
-cd /tmp && TMPDIR=/tmp timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$O/x2_prof -o run \
-    -- python3 $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 2 --no-cpu-baseline > $GRAFT_REPO_ROOT/$O/x2_prof.log 2>&1 || exit 1
+R=$(pwd); cd /tmp && TMPDIR=/tmp timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/x2_prof -o run \
+    -- python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > $R/$O/x2_prof.log 2>&1 || exit 1

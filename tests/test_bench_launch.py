@@ -14,8 +14,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
 
 
-def _run(args, env_extra=None, timeout=120):
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+def _run(args, env_extra=None, timeout=120, drop=()):
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK") + tuple(drop)}
     env.update(env_extra or {})
     return subprocess.run([sys.executable, BENCH] + args, capture_output=True, text=True, env=env, timeout=timeout)
 
@@ -79,10 +79,12 @@ def test_gpu_count_from_sysfs(tmp_path, monkeypatch):
 
 def test_launcher_counts_gpus_from_sysfs(tmp_path):
     # the launcher process counts the devices from the KFD topology (no HIP call in the parent)
+    # (a visibility mask of the caller's would narrow the made-up topology: the launcher runs without one)
     _fake_kfd(tmp_path, 4)
     env = {"FASTKMER_KFD_TOPOLOGY": str(tmp_path)}
-    p = _run(["--gpus", "4", "--steps", "1", "--dry-run"], env)
+    mask = ("HIP_VISIBLE_DEVICES", "ROCR_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES")
+    p = _run(["--gpus", "4", "--steps", "1", "--dry-run"], env, drop=mask)
     assert p.returncode == 0, p.stderr
     assert json.loads(p.stdout.strip().splitlines()[-1])["visible_gpus"] == 4
-    p = _run(["--gpus", "8", "--steps", "1"], env)
+    p = _run(["--gpus", "8", "--steps", "1"], env, drop=mask)
     assert p.returncode == 2 and "only 4 GPU(s) visible" in p.stderr
