@@ -243,11 +243,21 @@ struct SortedPlan {
     uint64_t max_bin = 0;  // the largest bin's k-mers the plan was made for
 };
 
-}  // namespace
+// A stream and the scan workspace its scans use.  The count's stages take one as a parameter: the
+// context's own (`stream`, `ws`) or the staging stream's (`xstage`, `ws_x`); see main_on / stage_on.
+// A scan owns its workspace from launch to completion, so two streams share one only while their
+// scans are ordered by events.  The side stream (`tier_side`) borrows the main stream's workspace
+// under this rule: its scans (the last piece's bucket cut, the split's sizes) are queued behind a wait
+// for an event recorded on the main stream after that stream's last scan (side_ev[2] after the
+// cell-offset scan of the last piece, or side_ev[3] behind the cut), and the main stream queues no scan
+// again until it has waited for the side stream's work (side_ev[0] after the cut, side_ev[1] after the
+// heavy tiers: the result's scans follow it).
+struct StreamWs {
+    hipStream_t s;
+    ScanWorkspace *ws;
+};
 
-#ifndef FK_SIDE_PRIO
-#define FK_SIDE_PRIO 1  // A/B builds: -DFK_SIDE_PRIO=0 the heavy tiers' stream at normal priority
-#endif
+}  // namespace
 
 struct fk_ctx {
     fk_config cfg{};
@@ -272,10 +282,12 @@ struct fk_ctx {
     bool split_retry = false;  // FASTKMER_DEBUG_SPLIT_RETRY: every split bucket cut a second time
     int x2_l1 = 0;             // FASTKMER_X2_L1: level-1 workgroup size (512, 1024; 0 = by fan-out)
     int fused = 1;             // FASTKMER_FUSED=0: two-kernel map (parse, then signature) for every input
+#ifdef FK_PROBES
     // Measurement-only (a library built with -DFK_PROBES; wrong results by design):
     int dbg_phase = 99;        // FASTKMER_DEBUG_PHASE: stop the bucket kernel early
     int fused_probe = 0;       // FASTKMER_FUSED_PROBE: stop the fused map kernel after a phase
     int split_map = 0;         // FASTKMER_SPLIT_MAP=1: the map as a parse kernel + a signature-pass kernel
+#endif
     bool last_map_fused = false;  // the last fk_map used the fused kernel (stats, tests)
     // grouped emit (fk_set_grouped_emit): send buffer grouped by (destination, local bin)
     bool grouped = false;
@@ -291,10 +303,9 @@ struct fk_ctx {
     void *pinned[2] = {nullptr, nullptr};  // staging for pageable sources
     hipEvent_t pin_ev[2] = {nullptr, nullptr};
     hipStream_t copy_stream = nullptr;     // H2D of fk_ingest (the map runs on `stream` meanwhile)
-    hipStream_t tier_side = nullptr;       // the count's heavy tiers beside the wave tier (FK_TIER_SIDE)
+    hipStream_t tier_side = nullptr;       // the count's heavy tiers beside the wave tier, the last piece's cut
     // [0] cut -> wave tier, [1] heavy tiers -> result, [2] last piece's cell offsets -> cut, [3] -> heavy
     hipEvent_t side_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    bool cut_side = false;                 // the last staged piece: the job's bucket cut beside its expansion
     hipEvent_t seg_ev = nullptr;           // "segment landed" (copy stream -> map stream)
     hipEvent_t h2d_ev[2] = {nullptr, nullptr};  // first copy issued / last copy done (timing)
     // streamed map (fused path): fk_ingest maps every tile whose bytes (and halo) have landed
@@ -399,6 +410,8 @@ struct fk_ctx {
     hipStream_t xstage = nullptr;
     hipEvent_t xstage_ev = nullptr;
     ScanWorkspace ws_x;
+    StreamWs main_on() { return StreamWs{stream, &ws}; }
+    StreamWs stage_on() { return StreamWs{xstage, &ws_x}; }
     hipEvent_t emit_ev = nullptr;                // map stream: a piece's send records are written
     std::vector<hipEvent_t> xev;                 // comm stream: begin / end of every piece's transfer
     uint64_t piece_bytes = 512ull << 20;         // FASTKMER_PIECE_BYTES: FASTA bytes per piece (with a
@@ -429,6 +442,17 @@ struct fk_ctx {
 // ---------------------------------------------------------------------------
 
 FK_EXPORT int fk_abi_version(void) { return FK_ABI_VERSION; }
+
+// The measurement probes' settings (-DFK_PROBES); the product library has none.
+#ifdef FK_PROBES
+static int bucket_probe_phase(const fk_ctx *c) { return c->dbg_phase; }  // 99: none
+static int fused_probe(const fk_ctx *c) { return c->fused_probe; }
+static bool map_split(const fk_ctx *c) { return c->split_map && !c->fused_probe; }
+#else
+static int bucket_probe_phase(const fk_ctx *) { return 99; }
+static int fused_probe(const fk_ctx *) { return 0; }
+static bool map_split(const fk_ctx *) { return false; }
+#endif
 
 // Host waits on work that may depend on the exchange (the comm stream, the staging stream that waits
 // for a step's transfer, events behind them): with a communicator they are bounded (Comm::wait: RCCL
@@ -621,13 +645,13 @@ FK_EXPORT int fk_create(const fk_config *cfg, fk_ctx **out) {
     // later segments never queues behind a piece's expansion; the exchange: the received segments)
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->xstage, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->xstage_ev, hipEventDisableTiming);
-    // the heavy tiers' stream at the device's highest priority (FK_SIDE_PRIO): their kernels are few
+    // the heavy tiers' stream at the device's highest priority: their kernels are few
     // and long chains (split, in-order sub-buckets, fallbacks with large workgroups), and at normal
     // priority they waited for LDS behind the wave tier's millions of one-wave workgroups and ran
     // alone after it (the configs[2] load's split fallbacks: 13.8 ms of a kernel of ~40 workgroups)
     if (e == hipSuccess) {
         int least = 0, greatest = 0;
-        if (FK_SIDE_PRIO && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess)
+        if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess)
             e = hipStreamCreateWithPriority(&c->tier_side, hipStreamNonBlocking, greatest);
         else
             e = hipStreamCreateWithFlags(&c->tier_side, hipStreamNonBlocking);
@@ -670,6 +694,8 @@ FK_EXPORT void fk_destroy(fk_ctx *c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     // staged expansions (an ingest without fk_finish) read the buffers released below
     if (c->xstage) (void)hipStreamSynchronize(c->xstage);
+    // and the heavy tiers of a count that failed half way
+    if (c->tier_side) (void)hipStreamSynchronize(c->tier_side);
     DevBuf *bufs[] = {&c->fasta_own, &c->tile_last_nl, &c->tile_off,
                       &c->npos_dev, &c->codes, &c->valid, &c->records, &c->counters, &c->sig_status, &c->sig_kmers, &c->tcnt, &c->rec_hdr, &c->rec_pos, &c->rec_code, &c->tstat, &c->map_vslots,
                       &c->precs, &c->chunks, &c->bin_chunk_begin, &c->hpieces, &c->hpiece_first, &c->hpiece_tot, &c->chunk_nk, &c->grp_table,
@@ -790,7 +816,6 @@ static bool premap_eligible(const fk_ctx *c) {
 // kernel's waves keep the SIMDs busy), or the fused kernel (FASTKMER_SPLIT_MAP=0, the 256-thread
 // tiles, probes).  map_vslots is sized by the callers (map_vslots_reserve).
 constexpr uint64_t MAP_VSLOT_TILES = 32768;  // ~1.07 GB of FASTA per split launch pair (140 MB of slots)
-static bool map_split(const fk_ctx *c) { return c->split_map && !c->fused_probe; }
 static int map_vslots_reserve(fk_ctx *c, uint64_t ntiles) {
     if (!map_split(c)) return FK_OK;
     return ensure(c->map_vslots, std::min(ntiles, MAP_VSLOT_TILES) * map_fused_vslot() * 4);
@@ -802,7 +827,7 @@ static int map_launch(fk_ctx *c, const uint8_t *fa, uint64_t n, int more, uint64
         HIP_TRY(launch_map_fused(FUSED_NT, c->cfg.k, c->cfg.m, fa, n, more, t0 + b, m, c->fm,
                                  c->rec_hdr.as<uint32_t>(), c->rec_pos.as<uint16_t>(), c->rec_code.as<uint32_t>(),
                                  c->tcnt.as<uint32_t>(), c->tstat.as<uint32_t>(), c->counters.as<unsigned long long>(),
-                                 s, c->fused_probe, cap ? c->map_vslots.as<uint32_t>() : nullptr));
+                                 s, fused_probe(c), cap ? c->map_vslots.as<uint32_t>() : nullptr));
         b += m;
     }
     return FK_OK;
@@ -860,6 +885,7 @@ static int ingest_impl(fk_ctx *c, const uint8_t *fasta, size_t n, int last) {
             xch_reset(c);
         }
         FK_TRY(comm_sync(c, c->xstage));
+        HIP_TRY(hipStreamSynchronize(c->tier_side));  // (the heavy tiers of a count that failed half way)
         HIP_TRY(hipStreamSynchronize(s));  // a previous job's work may still read the buffers
         pieces_reset(c);
         c->pm_active = premap_eligible(c);
@@ -912,10 +938,7 @@ static int ingest_impl(fk_ctx *c, const uint8_t *fasta, size_t n, int last) {
         // step ends (1 GB steps of a 6.25 GB job staged 5-6 GB after the last byte: 11 ms of expansion
         // in the tail, profiles/r05d_xch1_c3_tail.txt)
         constexpr uint64_t XCH_STEPS = 10;
-#ifndef FK_XCH_MIN_MB
-#define FK_XCH_MIN_MB 64  // 1 GB job: ten steps (A/B builds: 128, seven steps)
-#endif
-        constexpr uint64_t XCH_MIN = (uint64_t)FK_XCH_MIN_MB << 20;
+        constexpr uint64_t XCH_MIN = 64ull << 20;  // a 1 GB job: ten steps (128 MB: seven)
         if (!c->piece_bytes_set)
             c->piece_bytes = c->xch.expect_bytes
                                  ? std::min<uint64_t>(1ull << 30, std::max<uint64_t>(XCH_MIN, c->xch.expect_bytes / XCH_STEPS))
@@ -1559,6 +1582,16 @@ FK_EXPORT int fk_bin_owners(const fk_ctx *c, int32_t *owner) {
 // reduce side
 // ---------------------------------------------------------------------------
 
+// The tiered count, and with it staged pieces (one rank's landed pieces, or the received segments):
+// k <= 63 (k = 64 counts the whole input after the last byte, one workgroup per bucket; so do the
+// test hook that routes every bucket through the streaming path and the bucket-kernel probes)
+static bool staged_ok(const fk_ctx *c) {
+#ifdef FK_PROBES
+    if (c->dbg_phase != 99) return false;
+#endif
+    return c->cfg.k <= 63 && !c->force_large;
+}
+
 static SortedPlan sorted_plan(const fk_ctx *c, uint64_t max_bin_kmers) {
     SortedPlan pl;
     const int k = c->cfg.k;
@@ -1571,14 +1604,12 @@ static SortedPlan sorted_plan(const fk_ctx *c, uint64_t max_bin_kmers) {
     // half the cell words: configs[2] load 146.9 -> 146.3 ms, configs[1] equal,
     // profiles/r06r_cell_target.txt; 128-bit keys keep 128 per cell)
     // k = 64 (no spare bit in a 128-bit key's hi word): one-level scatter, one workgroup per bucket
-    const bool tiered = c->cfg.k <= 63 && c->dbg_phase == 99 && !c->force_large;
+    const bool tiered = staged_ok(c);
     const bool two_level = c->cfg.k <= 63;
-#ifndef FK_CELL_TARGET64
-#define FK_CELL_TARGET64 512  // A/B builds: keys per cell of the largest bin, 64-bit keys, two levels
-#endif
+    constexpr uint64_t CELL_TARGET64 = 512;  // keys per cell of the largest bin, 64-bit keys, two levels
     const uint64_t target = c->cell_target ? c->cell_target
                                            : (c->KW == 2 && tiered ? WAVE128_BUCKET_CAP / 2
-                                                                   : two_level ? FK_CELL_TARGET64 : cap / 4);
+                                                                   : two_level ? CELL_TARGET64 : cap / 4);
     int F = 1;
     while (F < MAX_FINE_BITS && ((uint64_t)1 << F) * target < max_bin_kmers) ++F;
     if (!two_level) F = std::min(F, MAX_FINE_BITS - 1);  // one-level scatter: 8 << F bytes of LDS <= 128 KB
@@ -1594,10 +1625,11 @@ static SortedPlan sorted_plan(const fk_ctx *c, uint64_t max_bin_kmers) {
 
 // 4: expand the records (chunk table at c->chunks, records at c->rsrc) into canonical k-mers laid
 // out bin-major by cell in `keys`; c->cell_total = the cell totals, `cell_base` their exclusive
-// scan (ncell_all + 1 entries)
-static int sorted_expand(fk_ctx *c, const SortedPlan &pl, uint32_t nchunks, uint64_t total_kmers, DevBuf &keys,
-                         DevBuf &cell_base_buf) {
-    hipStream_t s = c->stream;
+// scan (ncell_all + 1 entries).  Queued on `on`; `cut` (or null): the side stream on which the job's
+// bucket cut follows the cell offsets, beside the expansion levels (side_ev[2] tells it)
+static int sorted_expand(fk_ctx *c, StreamWs on, hipStream_t cut, const SortedPlan &pl, uint32_t nchunks,
+                         uint64_t total_kmers, DevBuf &keys, DevBuf &cell_base_buf) {
+    hipStream_t s = on.s;
     const int k = c->cfg.k;
     const int F = pl.F, F2 = pl.F2, F1 = pl.F1;
     const bool two_level = pl.two_level;
@@ -1654,8 +1686,8 @@ static int sorted_expand(fk_ctx *c, const SortedPlan &pl, uint32_t nchunks, uint
         HIP_TRY(launch_cell_prefix(c->bin_chunk_begin.as<uint32_t>(), c->nlb, F, c->lp.as<uint32_t>(),
                                    c->cell_total.as<uint64_t>(), s));
     }
-    HIP_TRY(scan_excl_sum_u64(c->cell_total.as<uint64_t>(), cell_base, ncell_all, cell_base + ncell_all, c->ws, s));
-    if (c->cut_side) HIP_TRY(hipEventRecord(c->side_ev[2], s));  // the cell totals and offsets are ready
+    HIP_TRY(scan_excl_sum_u64(c->cell_total.as<uint64_t>(), cell_base, ncell_all, cell_base + ncell_all, *on.ws, s));
+    if (cut) HIP_TRY(hipEventRecord(c->side_ev[2], s));  // the cell totals and offsets are ready
     if (two_level) {
         FK_TRY(ensure(c->mid, total_kmers * 8 * c->KW));
         HIP_TRY(launch_expand_two_level(c->KW, c->rsrc, c->chunks.as<Chunk>(), nchunks, c->nlb, k, F,
@@ -1668,9 +1700,7 @@ static int sorted_expand(fk_ctx *c, const SortedPlan &pl, uint32_t nchunks, uint
     return FK_OK;
 }
 
-// 4c + 5: buckets over c->cell_total / c->cell_base (the job's cells), their exact counts from
-// `src` (one key array, or the staged pieces'), the dense result and its bin offsets
-// The buffers of one bucket cut and its counts (the job's, or a staged job's pre-count).
+// The buffers of one bucket cut and its counts.
 struct CountBufs {
     DevBuf *flags, *flag_scan, *buckets, *bucket_unique, *tier_list, *piece_starts, *out_counts;
 };
@@ -1679,322 +1709,380 @@ static CountBufs main_bufs(fk_ctx *c) {
                      &c->out_counts};
 }
 
-// The listed buckets of at most cap keys above skip_le keys (skip_le: counted by a mid wave tier) in one
-// workgroup's LDS: the block kernel (64-bit keys) or the LDS radix sort (128-bit keys).
-static int block_tier(fk_ctx *c, const BucketSrc &src, CountBufs B, DevBuf &okb, const uint32_t *list, uint32_t n,
-                      uint32_t cap, uint32_t skip_le, hipStream_t s) {
-    if (c->KW == 1)
-        HIP_TRY(launch_bucket_count64(src, B.buckets->as<Bucket>(), n, c->cfg.k, okb.as<uint64_t>(),
-                                      B.out_counts->as<uint32_t>(), B.bucket_unique->as<uint64_t>(),
-                                      c->misc.as<unsigned long long>() + 1, cap, 99, list, s, skip_le));
-    else
-        HIP_TRY(launch_bucket_sort(2, src, B.buckets->as<Bucket>(), n, c->cfg.k, okb.as<uint64_t>(),
-                                   B.out_counts->as<uint32_t>(), B.bucket_unique->as<uint64_t>(),
-                                   c->misc.as<unsigned long long>() + 1, cap, list, s, skip_le));
-    return FK_OK;
-}
-
-// 4c + 5: buckets over cell_total / cell_base (ncell_all cells), their exact counts from `src` (one
-// key array, or the staged pieces') into okb / B.out_counts at each bucket's first slot, the
-// distinct keys per bucket in B.bucket_unique; *nb_out = buckets
-static int sorted_count_buckets(fk_ctx *c, const SortedPlan &pl, const BucketSrc &src_in, uint64_t total_kmers,
-                                const uint64_t *cell_total, const uint64_t *cell_base, CountBufs B, DevBuf &okb,
-                                uint64_t *nb_out) {
-    hipStream_t s = c->stream;
-    // the cut's stream: `s`, or beside the last staged piece's expansion (cut_side)
-    const hipStream_t cs = c->cut_side ? c->tier_side : s;
-    const int k = c->cfg.k;
-    const int F = pl.F;
-    const bool tiered = pl.tiered;
-    const uint32_t cap = pl.cap, wave_cap = pl.wave_cap;
-    const uint64_t ncell_all = (uint64_t)c->nlb << F;
+// 4c + 5: one count of a job's buckets -- the cut of the cells (ncell_all of them) into buckets, then
+// every bucket's exact count from `src` (one key array, or the staged pieces') into okb / out_counts
+// at the bucket's first slot, its distinct keys in bucket_unique.  What the steps below share:
+struct BucketCount {
+    fk_ctx *c;
+    BucketSrc src;  // the cut sets F and the staged pieces' starts
+    CountBufs B;
+    DevBuf &okb;
+    int k;
+    uint32_t cap;  // keys of the largest bucket one workgroup's LDS holds
     // useHT=1 (extractKXmersHT, SBKC:664-739): the wave tiers' LDS hash tables emit their keys in
     // table order (the reference writes its hash map's iteration order, SBKC:723-734), no rank; the
     // heavier tiers' outputs stay ascending, which is one such order too
-    const bool ordered = !c->cfg.use_ht;
+    bool ordered;
+    // s: the wave tier, and the result after it.  cut: the bucket cut -- s, or the side stream beside
+    // the last staged piece's expansion.  heavy: the tiers above the wave tier, on the side stream
+    // (both with s's workspace: StreamWs)
+    StreamWs s, cut, heavy;
+    uint64_t nbuckets = 0;
+    // the tiers above the wave tier, read back from pinned memory behind the tier kernel:
+    // lists[0 .. ntier[0]) the block tier's buckets (up to mid_cap() keys), lists[nbuckets ..
+    // nbuckets + ntier[1]) the big tier's; listed_keys = their keys
+    uint32_t *lists = nullptr;
+    uint32_t ntier[2] = {0, 0};
+    uint64_t listed_keys = 0;
+    // what the 64-bit mid tier's first kernel and the split leave: the buckets for the 1024-key kernel
+    // (mid_fb), for the block path (fbB) and for the big-table / streaming path (fbG)
+    bool mid_wave = false;
+    uint32_t *mid_fb = nullptr, *fbB = nullptr, *fbG = nullptr;
+    uint32_t nmidfb = 0, nfbB = 0, nfbG = 0;
+
+    const Bucket *buckets() const { return B.buckets->as<Bucket>(); }
+    uint64_t *out_keys() const { return okb.as<uint64_t>(); }
+    uint32_t *out_counts() const { return B.out_counts->as<uint32_t>(); }
+    uint64_t *unique() const { return B.bucket_unique->as<uint64_t>(); }
+    uint32_t mid_cap() const { return c->KW == 1 ? WAVE_MID_CAP : WAVE128_MID_CAP; }
+    unsigned int *mid_fb_count() const { return c->misc.as<unsigned int>() + 11; }
+};
+
+// 64- / 128-bit keys: the same launch with the other kernel (and its sub-bucket type)
+static hipError_t launch_wave_tier(const BucketCount &t, hipStream_t s) {
+    if (t.c->KW == 1)
+        return launch_bucket_count64_wave(t.src, t.buckets(), t.nbuckets, t.k, t.out_keys(), t.out_counts(), t.unique(),
+                                          nullptr, s, t.ordered);
+    return launch_bucket_count128_wave(t.src, t.buckets(), t.nbuckets, t.k, t.out_keys(), t.out_counts(), t.unique(), s,
+                                       t.ordered);
+}
+static hipError_t launch_wave_mid(const BucketCount &t, const uint32_t *list, uint32_t n, hipStream_t s) {
+    if (t.c->KW == 1)
+        return launch_bucket_count64_wave_mid(t.src, t.buckets(), list, n, t.k, t.out_keys(), t.out_counts(), t.unique(),
+                                              s, t.ordered);
+    return launch_bucket_count128_wave_mid(t.src, t.buckets(), list, n, t.k, t.out_keys(), t.out_counts(), t.unique(), s,
+                                           t.ordered);
+}
+static hipError_t launch_split(const BucketCount &t, const uint32_t *l1, uint32_t nl, SubBucket *subs,
+                               unsigned int *counts, uint32_t *fb, hipStream_t s) {
+    fk_ctx *c = t.c;
+    return launch_bucket_split64(t.src, t.buckets(), t.lists, 0, l1, nl, c->sp_base.as<uint64_t>(),
+                                 c->sp_keys.as<uint64_t>(), subs, c->sp_par.as<SplitParent>(), counts, fb, fb + nl,
+                                 t.cap, t.k, t.src.F, s, c->split_retry);
+}
+static hipError_t launch_split(const BucketCount &t, const uint32_t *l1, uint32_t nl, SubBucket128 *subs,
+                               unsigned int *counts, uint32_t *fb, hipStream_t s) {
+    fk_ctx *c = t.c;
+    return launch_bucket_split128(t.src, t.buckets(), l1, nl, c->sp_base.as<uint64_t>(), c->sp_keys.as<uint64_t>(), subs,
+                                  c->sp_par.as<SplitParent>(), counts, fb, fb + nl, t.cap, t.k, t.src.F, s,
+                                  c->split_retry);
+}
+static hipError_t launch_sub_count_seq(const BucketCount &t, const uint32_t *l1, uint32_t nl, const SubBucket *subs,
+                                       hipStream_t s) {
+    return launch_sub_count64_seq(t.buckets(), l1, nl, t.c->sp_par.as<SplitParent>(), subs, t.c->sp_keys.as<uint64_t>(),
+                                  t.out_keys(), t.out_counts(), t.unique(), s, t.ordered);
+}
+static hipError_t launch_sub_count_seq(const BucketCount &t, const uint32_t *l1, uint32_t nl, const SubBucket128 *subs,
+                                       hipStream_t s) {
+    return launch_sub_count128_seq(t.buckets(), l1, nl, t.c->sp_par.as<SplitParent>(), subs, t.c->sp_keys.as<uint64_t>(),
+                                   t.out_keys(), t.out_counts(), t.unique(), s, t.ordered);
+}
+
+// The listed buckets of at most cap keys in one workgroup's LDS: the block kernel (64-bit keys) or
+// the LDS radix sort (128-bit keys).
+static int block_tier(const BucketCount &t, const uint32_t *list, uint32_t n, hipStream_t s) {
+    fk_ctx *c = t.c;
+    if (c->KW == 1)
+        HIP_TRY(launch_bucket_count64(t.src, t.buckets(), n, t.k, t.out_keys(), t.out_counts(), t.unique(),
+                                      c->misc.as<unsigned long long>() + 1, t.cap, 99, list, s, 0));
+    else
+        HIP_TRY(launch_bucket_sort(2, t.src, t.buckets(), n, t.k, t.out_keys(), t.out_counts(), t.unique(),
+                                   c->misc.as<unsigned long long>() + 1, t.cap, list, s, 0));
+    return FK_OK;
+}
+
+// 4c: buckets.  Tiered (k <= 63): cells packed greedily into buckets of <= wave_cap keys for the wave
+// kernel, larger cells to the tiers above it.  Otherwise buckets of <= cap keys.
+static int bucket_cut(BucketCount &t, const SortedPlan &pl, uint64_t total_kmers, const uint64_t *cell_total,
+                      const uint64_t *cell_base) {
+    fk_ctx *c = t.c;
+    const CountBufs &B = t.B;
+    const hipStream_t cs = t.cut.s;
+    const int F = pl.F;
+    const uint32_t cap = pl.cap;
+    const uint64_t ncell_all = (uint64_t)c->nlb << F;
     FK_TRY(ensure(*B.flags, ncell_all * 4));
     FK_TRY(ensure(*B.flag_scan, (ncell_all + 1) * 8));
     FK_TRY(ensure(c->misc, 64));
-    // 4c: buckets.  Tiered (k <= 32): cells packed greedily into buckets of
-    // <= wave_cap keys for the wave kernel, larger cells to the block kernel
-    // (<= cap) or the large path.  Otherwise buckets of <= cap keys.
-    if (tiered)
-        HIP_TRY(launch_bucket_flags_greedy(cell_total, c->nlb, F, wave_cap, -1, B.flags->as<uint32_t>(), cs));
+    if (pl.tiered)
+        HIP_TRY(launch_bucket_flags_greedy(cell_total, c->nlb, F, pl.wave_cap, -1, B.flags->as<uint32_t>(), cs));
     else
         HIP_TRY(launch_bucket_flags(cell_base, cell_total, c->nlb, F, cap / 4, cap - cap / 4, B.flags->as<uint32_t>(), cs));
     HIP_TRY(scan_excl_sum_u32_to_u64(B.flags->as<uint32_t>(), B.flag_scan->as<uint64_t>(), ncell_all,
-                                     B.flag_scan->as<uint64_t>() + ncell_all, c->ws, cs));
+                                     B.flag_scan->as<uint64_t>() + ncell_all, *t.cut.ws, cs));
     uint64_t nbuckets = 0;
     HIP_TRY(hipMemcpyAsync(&nbuckets, B.flag_scan->as<uint64_t>() + ncell_all, 8, hipMemcpyDeviceToHost, cs));
     HIP_TRY(hipStreamSynchronize(cs));
     htrace("sorted: nbuckets read");
+    t.nbuckets = nbuckets;
     FK_TRY(ensure(*B.buckets, nbuckets * sizeof(Bucket)));
-    FK_TRY(ensure(okb, total_kmers * 8 * c->KW));
+    FK_TRY(ensure(t.okb, total_kmers * 8 * c->KW));
     FK_TRY(ensure(*B.out_counts, total_kmers * 4));
     FK_TRY(ensure(*B.bucket_unique, (nbuckets + 1) * 8));
     HIP_TRY(launch_bucket_write(cell_base, B.flags->as<uint32_t>(), B.flag_scan->as<uint64_t>(), c->nlb, F, nbuckets,
                                 total_kmers, B.buckets->as<Bucket>(), cs));
-    BucketSrc src = src_in;
+    BucketSrc &src = t.src;
     src.F = F;
     if (src.np > 0) FK_TRY(ensure(*B.piece_starts, nbuckets * sizeof(PieceStarts)));
     // the buckets' sizes, and the staged pieces' starts per bucket (read by the wave tier)
     HIP_TRY(launch_bucket_finish(src, B.buckets->as<Bucket>(), nbuckets, c->nlb, total_kmers,
                                  src.np > 0 ? B.piece_starts->as<PieceStarts>() : nullptr, cs));
     if (src.np > 0) src.starts = B.piece_starts->as<PieceStarts>();
-    // 5: exact count per bucket in LDS; buckets that do not fit take the streaming path
-    const uint32_t small_limit = c->force_large ? 0u : cap;
     HIP_TRY(hipMemsetAsync(c->misc.p, 0, 64, cs));
     c->stats.buckets = nbuckets;
     c->stats.fine_bits = (uint64_t)F;
     c->stats.heavy_keys = 0;
     c->stats.split_buckets = c->stats.sub_buckets = 0;
-    if (tiered) {
-        FK_TRY(ensure(*B.tier_list, nbuckets * 8));
-        uint32_t *lists = B.tier_list->as<uint32_t>();
-#ifndef FK_SPLIT_HEAVY
-#define FK_SPLIT_HEAVY 1  // A/B builds (build_variant "nosplit", -DFK_SPLIT_HEAVY=0): no heavy-bucket split
-#endif
-        // the block tier's top: 64-bit keys with the split, the mid wave tier's cap (above it: split)
-        // (the 513..1024-key buckets through the split as well, no mid wave tier: configs[2] load
-        // 1.1-1.4 ms slower, configs[1] 0.3 ms, profiles/r05zg_mid_split_ab.txt)
-        const uint32_t block_top = FK_SPLIT_HEAVY ? (c->KW == 1 ? WAVE_MID_CAP : WAVE128_MID_CAP) : cap;
-        HIP_TRY(launch_bucket_tiers(B.buckets->as<Bucket>(), nbuckets, wave_cap, block_top,
-                                    B.bucket_unique->as<uint64_t>(), lists, c->misc.as<unsigned int>(),
-                                    c->misc.as<unsigned long long>() + 3, cs));
-        // the tier sizes (and the listed buckets' keys) go to pinned memory right behind the tier
-        // kernel: the host waits for that copy, not for the wave tier queued after it, before it
-        // queues the heavier tiers
-        if (c->pin_tier.ensure(64)) return set_err(FK_E_NOMEM, "hipHostMalloc failed");
-        HIP_TRY(hipMemcpyAsync(c->pin_tier.p, c->misc.p, 32, hipMemcpyDeviceToHost, cs));
-        HIP_TRY(hipEventRecord(c->tier_ev, cs));
-#ifndef FK_TIER_SIDE
-#define FK_TIER_SIDE 1  // A/B builds: -DFK_TIER_SIDE=0 the heavy tiers queued behind the wave tier
-#endif
-        // the heavier tiers (split, in-order sub-buckets, mid wave tier, fallbacks) run on their own
-        // stream beside the wave tier: their buckets, outputs and counters are disjoint from its, and
-        // the host's waits for the split's counts no longer wait for the wave tier
-        const hipStream_t hs = (FK_TIER_SIDE && c->tier_side) ? c->tier_side : s;
-        if (cs != s) {  // the wave tier after the cut (and, in stream order, the last piece's expansion)
-            HIP_TRY(hipEventRecord(c->side_ev[0], cs));
-            HIP_TRY(hipStreamWaitEvent(s, c->side_ev[0], 0));
-        }
-        if (hs != s) {  // the heavy tiers after both as well
-            HIP_TRY(hipEventRecord(c->side_ev[3], s));
-            HIP_TRY(hipStreamWaitEvent(hs, c->side_ev[3], 0));
-        }
-        // every bucket of <= wave_cap keys
-        if (c->KW == 1)
-            HIP_TRY(launch_bucket_count64_wave(src, B.buckets->as<Bucket>(), nbuckets, k,
-                                               okb.as<uint64_t>(), B.out_counts->as<uint32_t>(),
-                                               B.bucket_unique->as<uint64_t>(), nullptr, s, ordered));
-        else
-            HIP_TRY(launch_bucket_count128_wave(src, B.buckets->as<Bucket>(), nbuckets, k,
-                                                okb.as<uint64_t>(), B.out_counts->as<uint32_t>(),
-                                                B.bucket_unique->as<uint64_t>(), s, ordered));
-        HIP_TRY(hipEventSynchronize(c->tier_ev));
-        const uint32_t ntier[2] = {c->pin_tier.as<uint32_t>()[0], c->pin_tier.as<uint32_t>()[1]};
-        const uint64_t listed_keys = c->pin_tier.as<uint64_t>()[3];
-        c->stats.heavy_keys = listed_keys;
-        htrace("sorted: tiers read");
-        c->stats.block_buckets = ntier[0];
-        c->stats.big_buckets = ntier[1];
-        uint64_t nlarge = 0;
-        if (ntier[0] || ntier[1]) {
-            // Above the wave tier.  The block tier (up to the mid wave tier's cap: 1024 keys for 64-bit
-            // keys, 512 for 128-bit ones) is counted by the mid wave tier, one wave per bucket.  The big
-            // tier (above it) is split into wave-sized sub-buckets by sampled splitters and counted in
-            // order by one wave per bucket; a bucket with a sub-bucket too large for a wave (a k-mer
-            // repeated that often) falls back to the block kernel / LDS sort (<= cap keys) or the
-            // big-table kernel (64-bit) and the streaming path.  Without the split (-DFK_SPLIT_HEAVY=0,
-            // A/B builds) the block tier reaches cap and the block kernel / LDS sort takes its buckets
-            // above the mid wave tier's cap.
-            const bool w1 = c->KW == 1;
-            const uint32_t *l1 = lists + nbuckets;
-            uint32_t *fbB = nullptr, *fbG = lists + nbuckets;  // the fallback lists (block / big)
-            uint32_t nfbB = 0, nfbG = ntier[1];
-#ifndef FK_MID_PARTS
-#define FK_MID_PARTS 1  // A/B builds: -DFK_MID_PARTS=0 the 64-bit mid tier's buckets all on the 1024-key kernel
-#endif
-            constexpr uint32_t MID_PARTS_MIN = 1u << 17;  // mid-tier buckets from which the ranges kernel pays
-            // 64-bit mid tier: 2 or 3 key ranges per bucket on the wave tier's table (k_bucket_count64_parts);
-            // the buckets it leaves (a range above 512 keys) are listed for the 1024-key kernel.  Only for a
-            // large mid tier: the configs[2] load's 278 K mid buckets 146.5 -> 146.2 ms, but configs[1]'s 59 K
-            // 21.8 -> 21.95 ms (profiles/r06v_mid_parts_ab.txt).  A smaller mid tier (a job whose k-mers
-            // repeat: configs[1]) goes straight on the wave tier's table whole (k_bucket_count64_mid512), the
-            // buckets with more than 512 distinct keys listed for the 1024-key kernel.  Both run first on the
-            // side stream, ahead of the split.
-            const bool mid_wave = FK_MID_PARTS && w1 && ntier[0] && block_top == WAVE_MID_CAP && c->mid_parts != 0;
-            const bool parts = mid_wave && (c->mid_parts == 1 || (c->mid_parts != 2 && ntier[0] >= MID_PARTS_MIN));
-            uint32_t *mid_fb = nullptr, nmidfb = 0;
-            unsigned int *mid_fbc = c->misc.as<unsigned int>() + 11;
-            if (mid_wave) {
-                FK_TRY(ensure(c->mid_fb, (uint64_t)ntier[0] * 4));
-                mid_fb = c->mid_fb.as<uint32_t>();
-                if (parts)
-                    HIP_TRY(launch_bucket_count64_parts(src, B.buckets->as<Bucket>(), lists, ntier[0], k,
-                                                        okb.as<uint64_t>(), B.out_counts->as<uint32_t>(),
-                                                        B.bucket_unique->as<uint64_t>(), mid_fb, mid_fbc, hs, ordered));
-                else
-                    HIP_TRY(launch_bucket_count64_mid512(src, B.buckets->as<Bucket>(), lists, ntier[0], k,
-                                                         okb.as<uint64_t>(), B.out_counts->as<uint32_t>(),
-                                                         B.bucket_unique->as<uint64_t>(), mid_fb, mid_fbc, hs, ordered));
-            }
-            if (FK_SPLIT_HEAVY && ntier[1]) {  // nothing to split: no split kernels, no read-back
-                const uint32_t nl = ntier[1];
-                const uint64_t maxsub = listed_keys / 64 + nl + 64;  // >= ceil(n / SPL_TGT) sub-buckets per bucket
-                const size_t sub_bytes = w1 ? sizeof(SubBucket) : sizeof(SubBucket128);
-                FK_TRY(ensure(c->sp_base, ((uint64_t)nl + 1) * 8));
-                // 64-bit keys: a 512-key region per first-cut sub-bucket (split_room: <= 2 n + 512 per bucket)
-                FK_TRY(ensure(c->sp_keys, (w1 ? 2 * listed_keys + 512ull * nl : listed_keys) * 8 * c->KW));
-                FK_TRY(ensure(c->sp_subs, maxsub * sub_bytes));
-                FK_TRY(ensure(c->sp_par, (uint64_t)nl * sizeof(SplitParent)));
-                FK_TRY(ensure(c->sp_fb, (uint64_t)nl * 8));
-                uint32_t *fb = c->sp_fb.as<uint32_t>();
-                unsigned int *spc = c->misc.as<unsigned int>() + 8;  // [0] sub-buckets, [1] / [2] fallbacks
-                HIP_TRY(launch_listed_sizes(B.buckets->as<Bucket>(), lists, 0, l1, nl, c->sp_base.as<uint64_t>(), hs,
-                                            w1));
-                HIP_TRY(scan_excl_sum_u64(c->sp_base.as<uint64_t>(), c->sp_base.as<uint64_t>(), nl,
-                                          c->sp_base.as<uint64_t>() + nl, c->ws, hs));
-                if (w1)
-                    HIP_TRY(launch_bucket_split64(src, B.buckets->as<Bucket>(), lists, 0, l1, nl,
-                                                  c->sp_base.as<uint64_t>(), c->sp_keys.as<uint64_t>(),
-                                                  c->sp_subs.as<SubBucket>(), c->sp_par.as<SplitParent>(), spc, fb,
-                                                  fb + nl, cap, k, F, hs, c->split_retry));
-                else
-                    HIP_TRY(launch_bucket_split128(src, B.buckets->as<Bucket>(), l1, nl, c->sp_base.as<uint64_t>(),
-                                                   c->sp_keys.as<uint64_t>(), c->sp_subs.as<SubBucket128>(),
-                                                   c->sp_par.as<SplitParent>(), spc, fb, fb + nl, cap, k, F, hs,
-                                                   c->split_retry));
-                HIP_TRY(hipMemcpyAsync(c->pin_tier.as<uint8_t>() + 32, spc, 16, hipMemcpyDeviceToHost, hs));
-                HIP_TRY(hipEventRecord(c->tier_ev, hs));
-                HIP_TRY(hipEventSynchronize(c->tier_ev));
-                const uint32_t *sc = c->pin_tier.as<uint32_t>() + 8;
-                const uint32_t nsub = sc[0];
-                nmidfb = sc[3];  // misc word 11: the ranges kernel's fallbacks (queued before the copy)
-                fbB = fb, nfbB = sc[1], fbG = fb + nl, nfbG = sc[2];
-                htrace("sorted: split counts read");
-#ifdef FK_PROBES
-                if (w1 && getenv("FASTKMER_HOST_TRACE")) {  // the split buckets by size class: buckets, keys, fallbacks
-                    std::vector<uint64_t> base((size_t)nl + 1);
-                    std::vector<uint32_t> f(2 * (size_t)nl), h_l((size_t)nl);
-                    HIP_TRY(hipMemcpy(base.data(), c->sp_base.p, base.size() * 8, hipMemcpyDeviceToHost));
-                    HIP_TRY(hipMemcpy(f.data(), fb, f.size() * 4, hipMemcpyDeviceToHost));
-                    HIP_TRY(hipMemcpy(h_l.data(), l1, (size_t)nl * 4, hipMemcpyDeviceToHost));
-                    std::unordered_map<uint32_t, uint32_t> pos;
-                    for (uint32_t j = 0; j < nl; ++j) pos[h_l[j]] = j;
-                    uint64_t hb[40] = {}, hk[40] = {}, hf[40] = {}, hfk[40] = {};
-                    std::vector<char> isfb(nl, 0);
-                    for (uint32_t j = 0; j < sc[1]; ++j) isfb[pos[f[j]]] = 1;
-                    for (uint32_t j = 0; j < sc[2]; ++j) isfb[pos[f[nl + j]]] = 1;
-                    for (uint32_t j = 0; j < nl; ++j) {
-                        const uint64_t n = base[j + 1] - base[j];
-                        const int cl = 63 - __builtin_clzll(n | 1);
-                        hb[cl] += 1, hk[cl] += n;
-                        if (isfb[j]) hf[cl] += 1, hfk[cl] += n;
-                    }
-                    unsigned long long rk[4];
-                    HIP_TRY(hipDeviceSynchronize());
-                    HIP_TRY(rank_probe_read(rk, true));
-                    fprintf(stderr, "probe_rank (wave tier, before the split): iterations %llu keys %llu buckets %llu "
-                            "wall (small groups) %llu\n", rk[0], rk[1], rk[2], rk[3]);
-                    fprintf(stderr, "probe_split: split %u keys %llu subs %u fallbacks %u + %u\n", nl,
-                            (unsigned long long)base[nl], nsub, sc[1], sc[2]);
-                    for (int cl = 0; cl < 40; ++cl)
-                        if (hb[cl])
-                            fprintf(stderr, "probe_split: n in [2^%d, 2^%d): buckets %llu keys %llu fallback buckets %llu keys %llu\n",
-                                    cl, cl + 1, (unsigned long long)hb[cl], (unsigned long long)hk[cl],
-                                    (unsigned long long)hf[cl], (unsigned long long)hfk[cl]);
-                }
-#endif
-                if (nsub > maxsub) return set_err(FK_E_DEVICE, "bucket split: %u sub-buckets of at most %llu", nsub,
-                                                  (unsigned long long)maxsub);
-                if (w1)
-                    HIP_TRY(launch_sub_count64_seq(B.buckets->as<Bucket>(), l1, nl, c->sp_par.as<SplitParent>(),
-                                                   c->sp_subs.as<SubBucket>(), c->sp_keys.as<uint64_t>(),
-                                                   okb.as<uint64_t>(), B.out_counts->as<uint32_t>(),
-                                                   B.bucket_unique->as<uint64_t>(), hs, ordered));
-                else
-                    HIP_TRY(launch_sub_count128_seq(B.buckets->as<Bucket>(), l1, nl, c->sp_par.as<SplitParent>(),
-                                                    c->sp_subs.as<SubBucket128>(), c->sp_keys.as<uint64_t>(),
-                                                    okb.as<uint64_t>(), B.out_counts->as<uint32_t>(),
-                                                    B.bucket_unique->as<uint64_t>(), hs, ordered));
-                c->stats.split_buckets = nl - sc[1] - sc[2];
-                c->stats.sub_buckets = nsub;
-            }
-            if (mid_wave && !(FK_SPLIT_HEAVY && ntier[1])) {  // no split read-back: the fallbacks' count alone
-                HIP_TRY(hipMemcpyAsync(c->pin_tier.as<uint8_t>() + 44, mid_fbc, 4, hipMemcpyDeviceToHost, hs));
-                HIP_TRY(hipEventRecord(c->tier_ev, hs));
-                HIP_TRY(hipEventSynchronize(c->tier_ev));
-                nmidfb = c->pin_tier.as<uint32_t>()[11];
-            }
-            const uint32_t mid_cap = w1 ? WAVE_MID_CAP : WAVE128_MID_CAP;
-            if (ntier[0]) {
-                if (mid_wave) {
-                    if (nmidfb)
-                        HIP_TRY(launch_bucket_count64_wave_mid(src, B.buckets->as<Bucket>(), mid_fb, nmidfb, k,
-                                                               okb.as<uint64_t>(), B.out_counts->as<uint32_t>(),
-                                                               B.bucket_unique->as<uint64_t>(), hs, ordered));
-                } else if (w1)
-                    HIP_TRY(launch_bucket_count64_wave_mid(src, B.buckets->as<Bucket>(), lists, ntier[0], k,
-                                                           okb.as<uint64_t>(), B.out_counts->as<uint32_t>(),
-                                                           B.bucket_unique->as<uint64_t>(), hs, ordered));
-                else
-                    HIP_TRY(launch_bucket_count128_wave_mid(src, B.buckets->as<Bucket>(), lists, ntier[0], k,
-                                                            okb.as<uint64_t>(), B.out_counts->as<uint32_t>(),
-                                                            B.bucket_unique->as<uint64_t>(), hs, ordered));
-                if (block_top > mid_cap)  // no split: the block tier's buckets above the mid wave tier
-                    FK_TRY(block_tier(c, src, B, okb, lists, ntier[0], cap, mid_cap, hs));
-            }
-            if (nfbB) FK_TRY(block_tier(c, src, B, okb, fbB, nfbB, cap, 0, hs));
-            if (nfbG && w1) {
-                // above 2048 keys with at most 4096 distinct in one workgroup's LDS; others stay REDO
-                HIP_TRY(launch_bucket_count64_big(src, B.buckets->as<Bucket>(), nfbG, k, okb.as<uint64_t>(),
-                                                  B.out_counts->as<uint32_t>(), B.bucket_unique->as<uint64_t>(),
-                                                  c->misc.as<unsigned long long>() + 2, fbG, hs));
-                HIP_TRY(hipMemcpyAsync(&nlarge, c->misc.as<unsigned long long>() + 2, 8, hipMemcpyDeviceToHost, hs));
-                HIP_TRY(hipStreamSynchronize(hs));
-            } else if (nfbG) {
-                nlarge = nfbG;  // 128-bit keys: no big-table kernel
-            }
-            if (nlarge) {  // scratch for the listed buckets' keys only, taken by a cursor
-                FK_TRY(ensure(c->scratch, listed_keys * 8 * c->KW));
-                HIP_TRY(hipMemsetAsync(c->misc.as<unsigned long long>() + 6, 0, 8, hs));
-                HIP_TRY(launch_bucket_sort_large(c->KW, src, B.buckets->as<Bucket>(), nfbG, k,
-                                                 c->scratch.as<uint64_t>(), okb.as<uint64_t>(),
-                                                 B.out_counts->as<uint32_t>(), B.bucket_unique->as<uint64_t>(),
-                                                 fbG, hs, c->misc.as<unsigned long long>() + 6));
-            }
-        }
-        if (hs != s) {  // the result's scans follow both streams
-            HIP_TRY(hipEventRecord(c->side_ev[1], hs));
-            HIP_TRY(hipStreamWaitEvent(s, c->side_ev[1], 0));
-        }
-        c->stats.oversize_buckets = nlarge;
-    } else {
-        if (src.np > 0) return set_err(FK_E_INVALID, "staged pieces need the tiered count");
-        if (c->KW == 1)
-            HIP_TRY(launch_bucket_count64(src, B.buckets->as<Bucket>(), nbuckets, k,
-                                          okb.as<uint64_t>(), B.out_counts->as<uint32_t>(),
-                                          B.bucket_unique->as<uint64_t>(), c->misc.as<unsigned long long>(),
-                                          small_limit, c->dbg_phase, nullptr, s));
-        else
-            HIP_TRY(launch_bucket_sort(c->KW, src, B.buckets->as<Bucket>(), nbuckets, k,
-                                       okb.as<uint64_t>(), B.out_counts->as<uint32_t>(),
-                                       B.bucket_unique->as<uint64_t>(), c->misc.as<unsigned long long>(),
-                                       small_limit, nullptr, s));
-        uint64_t oversize = 0;
-        HIP_TRY(hipMemcpyAsync(&oversize, c->misc.p, 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        c->stats.oversize_buckets = oversize;
-        if (oversize) {
-            FK_TRY(ensure(c->scratch, total_kmers * 8 * c->KW));
-            HIP_TRY(launch_bucket_sort_large(c->KW, src, B.buckets->as<Bucket>(), nbuckets, k,
-                                             c->scratch.as<uint64_t>(), okb.as<uint64_t>(),
-                                             B.out_counts->as<uint32_t>(), B.bucket_unique->as<uint64_t>(),
-                                             nullptr, s));
-        }
+    return FK_OK;
+}
+
+// 5, tiered: the buckets above the wave tier listed by size, then every bucket of <= wave_cap keys on
+// s.  The heavier tiers (split, in-order sub-buckets, mid wave tier, fallbacks) run on their own
+// stream beside it: their buckets, outputs and counters are disjoint from its, and the host's waits
+// for the split's counts do not wait for the wave tier.
+static int wave_tier(BucketCount &t, uint32_t wave_cap) {
+    fk_ctx *c = t.c;
+    const hipStream_t s = t.s.s, cs = t.cut.s, hs = t.heavy.s;
+    FK_TRY(ensure(*t.B.tier_list, t.nbuckets * 8));
+    t.lists = t.B.tier_list->as<uint32_t>();
+    // the block tier's top is the mid wave tier's cap; above it, the split (the 513..1024-key buckets
+    // through the split as well, no mid wave tier: configs[2] load 1.1-1.4 ms slower, configs[1]
+    // 0.3 ms, profiles/r05zg_mid_split_ab.txt)
+    HIP_TRY(launch_bucket_tiers(t.buckets(), t.nbuckets, wave_cap, t.mid_cap(), t.unique(), t.lists,
+                                c->misc.as<unsigned int>(), c->misc.as<unsigned long long>() + 3, cs));
+    // the tier sizes (and the listed buckets' keys) go to pinned memory right behind the tier
+    // kernel: the host waits for that copy, not for the wave tier queued after it, before it
+    // queues the heavier tiers
+    if (c->pin_tier.ensure(64)) return set_err(FK_E_NOMEM, "hipHostMalloc failed");
+    HIP_TRY(hipMemcpyAsync(c->pin_tier.p, c->misc.p, 32, hipMemcpyDeviceToHost, cs));
+    HIP_TRY(hipEventRecord(c->tier_ev, cs));
+    if (cs != s) {  // the wave tier after the cut (and, in stream order, the last piece's expansion)
+        HIP_TRY(hipEventRecord(c->side_ev[0], cs));
+        HIP_TRY(hipStreamWaitEvent(s, c->side_ev[0], 0));
     }
-    *nb_out = nbuckets;
+    // the heavy tiers after both as well
+    HIP_TRY(hipEventRecord(c->side_ev[3], s));
+    HIP_TRY(hipStreamWaitEvent(hs, c->side_ev[3], 0));
+    HIP_TRY(launch_wave_tier(t, s));
+    HIP_TRY(hipEventSynchronize(c->tier_ev));
+    t.ntier[0] = c->pin_tier.as<uint32_t>()[0], t.ntier[1] = c->pin_tier.as<uint32_t>()[1];
+    t.listed_keys = c->pin_tier.as<uint64_t>()[3];
+    htrace("sorted: tiers read");
+    c->stats.heavy_keys = t.listed_keys;
+    c->stats.block_buckets = t.ntier[0];
+    c->stats.big_buckets = t.ntier[1];
+    return FK_OK;
+}
+
+// The 64-bit mid tier (the block tier's buckets, 513 .. 1024 keys) on the wave tier's 512-key table,
+// first on the side stream, ahead of the split: as 2 or 3 key ranges per bucket
+// (k_bucket_count64_parts; the buckets it leaves, a range above 512 keys, are listed in mid_fb), only
+// for a large mid tier: the configs[2] load's 278 K mid buckets 146.5 -> 146.2 ms, but configs[1]'s
+// 59 K 21.8 -> 21.95 ms (profiles/r06v_mid_parts_ab.txt).  A smaller mid tier (a job whose k-mers
+// repeat: configs[1]) goes on that table whole (k_bucket_count64_mid512), the buckets with more than
+// 512 distinct keys listed in mid_fb.  FASTKMER_DEBUG_MID_PARTS = 0: neither (mid_tier_rest takes all).
+static int mid_tier_first(BucketCount &t) {
+    fk_ctx *c = t.c;
+    constexpr uint32_t MID_PARTS_MIN = 1u << 17;  // mid-tier buckets from which the ranges kernel pays
+    t.mid_wave = c->KW == 1 && t.ntier[0] && c->mid_parts != 0;
+    if (!t.mid_wave) return FK_OK;
+    const bool parts = c->mid_parts == 1 || (c->mid_parts != 2 && t.ntier[0] >= MID_PARTS_MIN);
+    FK_TRY(ensure(c->mid_fb, (uint64_t)t.ntier[0] * 4));
+    t.mid_fb = c->mid_fb.as<uint32_t>();
+    if (parts)
+        HIP_TRY(launch_bucket_count64_parts(t.src, t.buckets(), t.lists, t.ntier[0], t.k, t.out_keys(), t.out_counts(),
+                                            t.unique(), t.mid_fb, t.mid_fb_count(), t.heavy.s, t.ordered));
+    else
+        HIP_TRY(launch_bucket_count64_mid512(t.src, t.buckets(), t.lists, t.ntier[0], t.k, t.out_keys(),
+                                             t.out_counts(), t.unique(), t.mid_fb, t.mid_fb_count(), t.heavy.s,
+                                             t.ordered));
+    return FK_OK;
+}
+
+#ifdef FK_PROBES
+// FASTKMER_HOST_TRACE: the split buckets by size class (buckets, keys, fallbacks) and the wave
+// tier's rank-loop counters before the split
+static int split_probe_dump(const BucketCount &t, const uint32_t *l1, uint32_t nl, const uint32_t *fb,
+                            const uint32_t *sc) {
+    fk_ctx *c = t.c;
+    std::vector<uint64_t> base((size_t)nl + 1);
+    std::vector<uint32_t> f(2 * (size_t)nl), h_l((size_t)nl);
+    HIP_TRY(hipMemcpy(base.data(), c->sp_base.p, base.size() * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(f.data(), fb, f.size() * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h_l.data(), l1, (size_t)nl * 4, hipMemcpyDeviceToHost));
+    std::unordered_map<uint32_t, uint32_t> pos;
+    for (uint32_t j = 0; j < nl; ++j) pos[h_l[j]] = j;
+    uint64_t hb[40] = {}, hk[40] = {}, hf[40] = {}, hfk[40] = {};
+    std::vector<char> isfb(nl, 0);
+    for (uint32_t j = 0; j < sc[1]; ++j) isfb[pos[f[j]]] = 1;
+    for (uint32_t j = 0; j < sc[2]; ++j) isfb[pos[f[nl + j]]] = 1;
+    for (uint32_t j = 0; j < nl; ++j) {
+        const uint64_t n = base[j + 1] - base[j];
+        const int cl = 63 - __builtin_clzll(n | 1);
+        hb[cl] += 1, hk[cl] += n;
+        if (isfb[j]) hf[cl] += 1, hfk[cl] += n;
+    }
+    unsigned long long rk[4];
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(rank_probe_read(rk, true));
+    fprintf(stderr, "probe_rank (wave tier, before the split): iterations %llu keys %llu buckets %llu "
+            "wall (small groups) %llu\n", rk[0], rk[1], rk[2], rk[3]);
+    fprintf(stderr, "probe_split: split %u keys %llu subs %u fallbacks %u + %u\n", nl,
+            (unsigned long long)base[nl], sc[0], sc[1], sc[2]);
+    for (int cl = 0; cl < 40; ++cl)
+        if (hb[cl])
+            fprintf(stderr, "probe_split: n in [2^%d, 2^%d): buckets %llu keys %llu fallback buckets %llu keys %llu\n",
+                    cl, cl + 1, (unsigned long long)hb[cl], (unsigned long long)hk[cl],
+                    (unsigned long long)hf[cl], (unsigned long long)hfk[cl]);
+    return FK_OK;
+}
+#endif
+
+// The big tier (above the mid wave tier's cap) split into wave-sized sub-buckets by sampled splitters
+// and counted in order by one wave per bucket; a bucket with a sub-bucket too large for a wave (a
+// k-mer repeated that often) is left to the block kernel / LDS sort (fbB: <= cap keys) or to the
+// big-table kernel (64-bit) and the streaming path (fbG).  Sub: SubBucket / SubBucket128.
+template <typename Sub>
+static int split_tier(BucketCount &t) {
+    fk_ctx *c = t.c;
+    const hipStream_t hs = t.heavy.s;
+    const bool w1 = c->KW == 1;
+    const uint32_t *l1 = t.lists + t.nbuckets;
+    const uint32_t nl = t.ntier[1];
+    const uint64_t maxsub = t.listed_keys / 64 + nl + 64;  // >= ceil(n / SPL_TGT) sub-buckets per bucket
+    FK_TRY(ensure(c->sp_base, ((uint64_t)nl + 1) * 8));
+    // 64-bit keys: a 512-key region per first-cut sub-bucket (split_room: <= 2 n + 512 per bucket)
+    FK_TRY(ensure(c->sp_keys, (w1 ? 2 * t.listed_keys + 512ull * nl : t.listed_keys) * 8 * c->KW));
+    FK_TRY(ensure(c->sp_subs, maxsub * sizeof(Sub)));
+    FK_TRY(ensure(c->sp_par, (uint64_t)nl * sizeof(SplitParent)));
+    FK_TRY(ensure(c->sp_fb, (uint64_t)nl * 8));
+    uint32_t *fb = c->sp_fb.as<uint32_t>();
+    unsigned int *spc = c->misc.as<unsigned int>() + 8;  // [0] sub-buckets, [1] / [2] fallbacks
+    HIP_TRY(launch_listed_sizes(t.buckets(), t.lists, 0, l1, nl, c->sp_base.as<uint64_t>(), hs, w1));
+    HIP_TRY(scan_excl_sum_u64(c->sp_base.as<uint64_t>(), c->sp_base.as<uint64_t>(), nl, c->sp_base.as<uint64_t>() + nl,
+                              *t.heavy.ws, hs));
+    HIP_TRY(launch_split(t, l1, nl, c->sp_subs.as<Sub>(), spc, fb, hs));
+    HIP_TRY(hipMemcpyAsync(c->pin_tier.as<uint8_t>() + 32, spc, 16, hipMemcpyDeviceToHost, hs));
+    HIP_TRY(hipEventRecord(c->tier_ev, hs));
+    HIP_TRY(hipEventSynchronize(c->tier_ev));
+    const uint32_t *sc = c->pin_tier.as<uint32_t>() + 8;
+    const uint32_t nsub = sc[0];
+    t.nmidfb = sc[3];  // misc word 11: the mid tier's leftovers (its kernel was queued before the copy)
+    t.fbB = fb, t.nfbB = sc[1], t.fbG = fb + nl, t.nfbG = sc[2];
+    htrace("sorted: split counts read");
+#ifdef FK_PROBES
+    if (w1 && getenv("FASTKMER_HOST_TRACE")) FK_TRY(split_probe_dump(t, l1, nl, fb, sc));
+#endif
+    if (nsub > maxsub)
+        return set_err(FK_E_DEVICE, "bucket split: %u sub-buckets of at most %llu", nsub, (unsigned long long)maxsub);
+    HIP_TRY(launch_sub_count_seq(t, l1, nl, c->sp_subs.as<Sub>(), hs));
+    c->stats.split_buckets = nl - sc[1] - sc[2];
+    c->stats.sub_buckets = nsub;
+    return FK_OK;
+}
+
+// The block tier's buckets not yet counted, one wave each on the mid wave tier's table (64-bit keys:
+// 1024 keys; 128-bit: 512): what mid_tier_first left, or all of them
+static int mid_tier_rest(BucketCount &t) {
+    fk_ctx *c = t.c;
+    const hipStream_t hs = t.heavy.s;
+    if (t.mid_wave && !t.ntier[1]) {  // no split read-back: the leftovers' count alone
+        HIP_TRY(hipMemcpyAsync(c->pin_tier.as<uint8_t>() + 44, t.mid_fb_count(), 4, hipMemcpyDeviceToHost, hs));
+        HIP_TRY(hipEventRecord(c->tier_ev, hs));
+        HIP_TRY(hipEventSynchronize(c->tier_ev));
+        t.nmidfb = c->pin_tier.as<uint32_t>()[11];
+    }
+    if (t.mid_wave) {
+        if (t.nmidfb) HIP_TRY(launch_wave_mid(t, t.mid_fb, t.nmidfb, hs));
+    } else if (t.ntier[0]) {
+        HIP_TRY(launch_wave_mid(t, t.lists, t.ntier[0], hs));
+    }
+    return FK_OK;
+}
+
+// What the split left: the block kernel / LDS sort (<= cap keys), the big-table kernel (64-bit keys:
+// above 2048 keys with at most 4096 distinct in one workgroup's LDS; the others stay REDO) and the
+// streaming path.  *nlarge = buckets on the streaming path.
+static int fallback_tiers(BucketCount &t, uint64_t *nlarge) {
+    fk_ctx *c = t.c;
+    const hipStream_t hs = t.heavy.s;
+    if (t.nfbB) FK_TRY(block_tier(t, t.fbB, t.nfbB, hs));
+    if (t.nfbG && c->KW == 1) {
+        HIP_TRY(launch_bucket_count64_big(t.src, t.buckets(), t.nfbG, t.k, t.out_keys(), t.out_counts(), t.unique(),
+                                          c->misc.as<unsigned long long>() + 2, t.fbG, hs));
+        HIP_TRY(hipMemcpyAsync(nlarge, c->misc.as<unsigned long long>() + 2, 8, hipMemcpyDeviceToHost, hs));
+        HIP_TRY(hipStreamSynchronize(hs));
+    } else if (t.nfbG) {
+        *nlarge = t.nfbG;  // 128-bit keys: no big-table kernel
+    }
+    if (*nlarge) {  // scratch for the listed buckets' keys only, taken by a cursor
+        FK_TRY(ensure(c->scratch, t.listed_keys * 8 * c->KW));
+        HIP_TRY(hipMemsetAsync(c->misc.as<unsigned long long>() + 6, 0, 8, hs));
+        HIP_TRY(launch_bucket_sort_large(c->KW, t.src, t.buckets(), t.nfbG, t.k, c->scratch.as<uint64_t>(), t.out_keys(),
+                                         t.out_counts(), t.unique(), t.fbG, hs,
+                                         c->misc.as<unsigned long long>() + 6));
+    }
+    return FK_OK;
+}
+
+// 5, k = 64 and the streaming-path test hook: every bucket by one workgroup (<= small_limit keys in
+// its LDS), the others on the streaming path
+static int whole_bucket_tier(BucketCount &t, uint64_t total_kmers) {
+    fk_ctx *c = t.c;
+    const hipStream_t s = t.s.s;
+    const uint32_t small_limit = c->force_large ? 0u : t.cap;
+    if (t.src.np > 0) return set_err(FK_E_INVALID, "staged pieces need the tiered count");
+    if (c->KW == 1)
+        HIP_TRY(launch_bucket_count64(t.src, t.buckets(), t.nbuckets, t.k, t.out_keys(), t.out_counts(), t.unique(),
+                                      c->misc.as<unsigned long long>(), small_limit, bucket_probe_phase(c), nullptr, s));
+    else
+        HIP_TRY(launch_bucket_sort(c->KW, t.src, t.buckets(), t.nbuckets, t.k, t.out_keys(), t.out_counts(), t.unique(),
+                                   c->misc.as<unsigned long long>(), small_limit, nullptr, s));
+    uint64_t oversize = 0;
+    HIP_TRY(hipMemcpyAsync(&oversize, c->misc.p, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    c->stats.oversize_buckets = oversize;
+    if (oversize) {
+        FK_TRY(ensure(c->scratch, total_kmers * 8 * c->KW));
+        HIP_TRY(launch_bucket_sort_large(c->KW, t.src, t.buckets(), t.nbuckets, t.k, c->scratch.as<uint64_t>(),
+                                         t.out_keys(), t.out_counts(), t.unique(), nullptr, s));
+    }
+    return FK_OK;
+}
+
+// The steps in order.  `cut` (or null): the side stream for the bucket cut, beside the last staged
+// piece's expansion on `on`.
+static int sorted_count_buckets(fk_ctx *c, StreamWs on, hipStream_t cut, const SortedPlan &pl, const BucketSrc &src,
+                                uint64_t total_kmers, const uint64_t *cell_total, const uint64_t *cell_base,
+                                CountBufs B, DevBuf &okb, uint64_t *nb_out) {
+    BucketCount t{c, src, B, okb, c->cfg.k, pl.cap, !c->cfg.use_ht,
+                  on, StreamWs{cut ? cut : on.s, on.ws}, StreamWs{c->tier_side, on.ws}};
+    FK_TRY(bucket_cut(t, pl, total_kmers, cell_total, cell_base));
+    *nb_out = t.nbuckets;
+    if (!pl.tiered) return whole_bucket_tier(t, total_kmers);
+    FK_TRY(wave_tier(t, pl.wave_cap));
+    uint64_t nlarge = 0;
+    if (t.ntier[0] || t.ntier[1]) {  // above the wave tier
+        FK_TRY(mid_tier_first(t));
+        if (t.ntier[1])  // nothing to split: no split kernels, no read-back
+            FK_TRY(c->KW == 1 ? split_tier<SubBucket>(t) : split_tier<SubBucket128>(t));
+        FK_TRY(mid_tier_rest(t));
+        FK_TRY(fallback_tiers(t, &nlarge));
+    }
+    // the result's scans follow both streams
+    HIP_TRY(hipEventRecord(c->side_ev[1], t.heavy.s));
+    HIP_TRY(hipStreamWaitEvent(t.s.s, c->side_ev[1], 0));
+    c->stats.oversize_buckets = nlarge;
     return FK_OK;
 }
 
@@ -2002,11 +2090,11 @@ static int sorted_count_buckets(fk_ctx *c, const SortedPlan &pl, const BucketSrc
 // bin_off per local bin (`flag_scan` of the bucket cut: a bin's first cell starts a bucket).  The
 // result stays bucket-major (no compaction pass): readers gather a bin's buckets (fk_get_bin) or the
 // whole result (fk_write_bins, materialize_dense).
-static int sorted_result(fk_ctx *c, int F, uint64_t nbuckets, DevBuf &okb, CountBufs B) {
-    hipStream_t s = c->stream;
+static int sorted_result(fk_ctx *c, StreamWs on, int F, uint64_t nbuckets, DevBuf &okb, CountBufs B) {
+    hipStream_t s = on.s;
     FK_TRY(ensure(c->dense_off, (nbuckets + 1) * 8));
     HIP_TRY(scan_excl_sum_u64(B.bucket_unique->as<uint64_t>(), c->dense_off.as<uint64_t>(), nbuckets,
-                              c->dense_off.as<uint64_t>() + nbuckets, c->ws, s));
+                              c->dense_off.as<uint64_t>() + nbuckets, *on.ws, s));
     FK_TRY(ensure(c->bin_off, ((uint64_t)c->nlb + 1) * 8));
     c->distinct_pending = true;
     HIP_TRY(launch_bin_offsets(B.flag_scan->as<uint64_t>(), c->dense_off.as<uint64_t>(), c->nlb, F, nbuckets,
@@ -2020,17 +2108,23 @@ static int sorted_result(fk_ctx *c, int F, uint64_t nbuckets, DevBuf &okb, Count
     return FK_OK;
 }
 
-static int sorted_count(fk_ctx *c, const SortedPlan &pl, const BucketSrc &src_in, uint64_t total_kmers) {
+static int sorted_count(fk_ctx *c, StreamWs on, hipStream_t cut, const SortedPlan &pl, const BucketSrc &src,
+                        uint64_t total_kmers) {
     // the two-level count writes its buckets' results over the first expansion level (`mid` is dead
     // once level 2 has run, stream order; a staged job's `mid` held one piece and grows to the job
     // here, its contents dead): one k-mer array less on the device (57 GB at configs[3]'s per-GPU
     // load, 128-bit keys; 36 GB at configs[2]'s)
     DevBuf &okb = pl.two_level ? c->mid : c->out_keys;
     uint64_t nb = 0;
-    FK_TRY(sorted_count_buckets(c, pl, src_in, total_kmers, c->cell_total.as<uint64_t>(), c->cell_base.as<uint64_t>(),
-                                main_bufs(c), okb, &nb));
-    return sorted_result(c, pl.F, nb, okb, main_bufs(c));
+    int rc = sorted_count_buckets(c, on, cut, pl, src, total_kmers, c->cell_total.as<uint64_t>(),
+                                  c->cell_base.as<uint64_t>(), main_bufs(c), okb, &nb);
+    if (rc == FK_OK) rc = sorted_result(c, on, pl.F, nb, okb, main_bufs(c));
+    // a failed count leaves nothing running on the side stream: its kernels read and write buffers
+    // that the next job reuses (on success the main stream has waited for it, side_ev[1])
+    if (rc != FK_OK) (void)hipStreamSynchronize(c->tier_side);
+    return rc;
 }
+
 
 // After the bin offsets are on the host: the sorted count's distinct total is their last entry.
 static void resolve_distinct(fk_ctx *c) {
@@ -2038,11 +2132,30 @@ static void resolve_distinct(fk_ctx *c) {
     c->distinct_pending = false;
 }
 
-static int reduce_sorted(fk_ctx *c, uint32_t nchunks, uint64_t total_kmers, uint64_t max_bin_kmers) {
+static int reduce_sorted(fk_ctx *c, StreamWs on, uint32_t nchunks, uint64_t total_kmers, uint64_t max_bin_kmers) {
     const SortedPlan pl = sorted_plan(c, max_bin_kmers);
-    FK_TRY(sorted_expand(c, pl, nchunks, total_kmers, c->keys, c->cell_base));
+    FK_TRY(sorted_expand(c, on, nullptr, pl, nchunks, total_kmers, c->keys, c->cell_base));
     BucketSrc src{c->keys.as<uint64_t>(), pl.F};
-    return sorted_count(c, pl, src, total_kmers);
+    return sorted_count(c, on, nullptr, pl, src, total_kmers);
+}
+
+// The end of a count queued on s: its bin offsets read back (the distinct total with them).
+static int read_bin_offsets(fk_ctx *c, hipStream_t s) {
+    const uint32_t nlb = c->nlb;
+    c->h_bin_off.assign((size_t)nlb + 1, 0);
+    if (c->pin_down.ensure(((size_t)nlb + 1) * 8)) return set_err(FK_E_NOMEM, "hipHostMalloc failed");
+    HIP_TRY(hipMemcpyAsync(c->pin_down.p, c->bin_off.p, ((uint64_t)nlb + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    memcpy(c->h_bin_off.data(), c->pin_down.p, ((size_t)nlb + 1) * 8);
+    resolve_distinct(c);
+    return FK_OK;
+}
+// ... and the stats every count ends with (ms_partition, ms_count: the caller's)
+static void count_done(fk_ctx *c, uint64_t nrecv, double t0) {
+    c->stats.records_received = nrecv;
+    c->stats.distinct = c->distinct;
+    c->stats.ms_total += now_ms() - t0;
+    c->have_result = true;
 }
 
 // Chunks of <= CHUNK_RECORDS records per local bin (chunks never span bins;
@@ -2070,7 +2183,8 @@ static void build_chunks(uint32_t nlb, const std::vector<std::vector<std::pair<u
 // The count over the chunk table (records at c->rsrc), bin offsets, stats.
 static int reduce_tail(fk_ctx *c, uint64_t nrecv, const std::vector<Chunk> &chunks, const std::vector<uint32_t> &bcb,
                        const std::vector<uint64_t> &bkm, double t0) {
-    hipStream_t s = c->stream;
+    const StreamWs on = c->main_on();
+    hipStream_t s = on.s;
     const uint32_t nlb = c->nlb;
     const uint32_t nchunks = (uint32_t)chunks.size();
     uint64_t total_kmers = 0, max_bin = 0;
@@ -2080,26 +2194,18 @@ static int reduce_tail(fk_ctx *c, uint64_t nrecv, const std::vector<Chunk> &chun
     }
     HIP_TRY(hipEventRecord(c->ev[6], s));
     // the sorted count; useHT=1 (extractKXmersHT) the same with the wave tiers in table order
-    FK_TRY(reduce_sorted(c, nchunks, total_kmers, max_bin));
+    FK_TRY(reduce_sorted(c, on, nchunks, total_kmers, max_bin));
     HIP_TRY(hipEventRecord(c->ev[7], s));
-    c->h_bin_off.assign((size_t)nlb + 1, 0);
-    if (c->pin_down.ensure(((size_t)nlb + 1) * 8)) return set_err(FK_E_NOMEM, "hipHostMalloc failed");
-    HIP_TRY(hipMemcpyAsync(c->pin_down.p, c->bin_off.p, ((uint64_t)nlb + 1) * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    memcpy(c->h_bin_off.data(), c->pin_down.p, ((size_t)nlb + 1) * 8);
-    resolve_distinct(c);
+    FK_TRY(read_bin_offsets(c, s));
     htrace("tail: bin offsets read");
-    c->stats.records_received = nrecv;
-    c->stats.distinct = c->distinct;
     c->stats.ms_partition = ev_ms(c->ev[4], c->ev[5]);
     c->stats.ms_count = ev_ms(c->ev[6], c->ev[7]);
-    c->stats.ms_total += now_ms() - t0;
-    c->have_result = true;
+    count_done(c, nrecv, t0);
     return FK_OK;
 }
 
-static int upload_chunks(fk_ctx *c, const std::vector<Chunk> &chunks, const std::vector<uint32_t> &bcb) {
-    hipStream_t s = c->stream;
+// the chunk table to the device, queued on s
+static int upload_chunks(fk_ctx *c, hipStream_t s, const std::vector<Chunk> &chunks, const std::vector<uint32_t> &bcb) {
     const uint32_t nchunks = (uint32_t)chunks.size();
     FK_TRY(ensure(c->chunks, nchunks * sizeof(Chunk)));
     FK_TRY(ensure(c->bin_chunk_begin, ((uint64_t)c->nlb + 1) * 4));
@@ -2120,14 +2226,14 @@ static int upload_chunks(fk_ctx *c, const std::vector<Chunk> &chunks, const std:
 }
 
 // partition of the records of `src` (all owned by this rank) by local bin into c->precs (the
-// count stage reads them at c->rsrc), the chunk table uploaded; bkm = k-mers per local bin
-static int partition_src(fk_ctx *c, const RecSrc &src, uint64_t &nrecv, std::vector<Chunk> &chunks,
+// count stage reads them at c->rsrc), the chunk table uploaded; bkm = k-mers per local bin.  Queued on `on`.
+static int partition_src(fk_ctx *c, StreamWs on, const RecSrc &src, uint64_t &nrecv, std::vector<Chunk> &chunks,
                          std::vector<uint32_t> &bcb, std::vector<uint64_t> &bkm, hipEvent_t e0, hipEvent_t e1) {
     nrecv = src.nrec;  // tiled sources: an upper bound, the partition counts them
-    hipStream_t s = c->stream;
+    hipStream_t s = on.s;
     const uint32_t nlb = c->nlb;
     HIP_TRY(hipEventRecord(e0, s));
-    FK_TRY(part_count(c->part, src, 1, c->G, local_table(c), nlb, c->ws, s));
+    FK_TRY(part_count(c->part, src, 1, c->G, local_table(c), nlb, *on.ws, s));
     htrace("reduce_src: part_count queued");
     // the scatter needs only the device-side offsets: it is queued before the host reads the part
     // totals (the output sized for src.nrec, for tiled sources the slot count: an upper bound), so
@@ -2176,7 +2282,7 @@ static int partition_src(fk_ctx *c, const RecSrc &src, uint64_t &nrecv, std::vec
         off = end;
     }
     bcb[nlb] = ci;
-    FK_TRY(upload_chunks(c, chunks, bcb));
+    FK_TRY(upload_chunks(c, s, chunks, bcb));
     htrace("reduce_src: chunks uploaded");
     HIP_TRY(hipEventRecord(e1, s));
     c->rsrc = c->precs.as<uint64_t>();
@@ -2191,7 +2297,7 @@ static int reduce_src(fk_ctx *c, const RecSrc &src) {
     std::vector<Chunk> chunks;
     std::vector<uint32_t> bcb;
     std::vector<uint64_t> bkm;
-    FK_TRY(partition_src(c, src, nrecv, chunks, bcb, bkm, c->ev[4], c->ev[5]));
+    FK_TRY(partition_src(c, c->main_on(), src, nrecv, chunks, bcb, bkm, c->ev[4], c->ev[5]));
     return reduce_tail(c, nrecv, chunks, bcb, bkm, t0);
 }
 
@@ -2247,7 +2353,7 @@ static int reduce_ranges(fk_ctx *c, const uint64_t *d_recv, uint64_t nrecv,
     std::vector<Chunk> chunks;
     std::vector<uint32_t> bcb;
     build_chunks(c->nlb, ranges, chunks, bcb);
-    FK_TRY(upload_chunks(c, chunks, bcb));
+    FK_TRY(upload_chunks(c, c->stream, chunks, bcb));
     HIP_TRY(hipEventRecord(c->ev[5], c->stream));
     c->rsrc = d_recv;
     return reduce_tail(c, nrecv, chunks, bcb, bkm, t0);
@@ -2309,12 +2415,6 @@ static const std::vector<double> &local_cuts(const fk_ctx *c) {
     return c->st_cuts;
 }
 
-// ---- staged pieces (sorted count, k <= 32): one rank's landed pieces, or the received segments
-// (k = 64 counts the whole input after the last byte; so do the test hook that routes every bucket
-// through the streaming path and the bucket-kernel probes)
-static bool staged_ok(const fk_ctx *c) {
-    return c->cfg.k <= 63 && c->dbg_phase == 99 && !c->force_large;
-}
 static bool staged_eligible(const fk_ctx *c) { return staged_ok(c) && c->G == 1 && !c->comm; }
 
 // Partitions one piece and expands it into its own key array (st_keys[p], its cells' exclusive
@@ -2323,9 +2423,12 @@ static bool staged_eligible(const fk_ctx *c) { return staged_ok(c) && c->G == 1 
 // Expands one piece's records (the chunk table at c->chunks, records at c->rsrc; bkm = k-mers per
 // local bin) into its own key array (st_keys[p], its cells' exclusive scan in st_cb[p]); the job's
 // cell totals accumulate in st_total.  `frac` = the piece's estimated fraction of the job (0:
-// unknown).  The first piece fixes the job's cells: its largest bin scaled to the job.
-static int staged_expand_chunks(fk_ctx *c, uint32_t nchunks, const std::vector<uint64_t> &bkm, double frac) {
-    hipStream_t s = c->stream;
+// unknown).  The first piece fixes the job's cells: its largest bin scaled to the job.  Queued on
+// `on`; `cut` (or null, the last piece only): the side stream that sums the job's cell totals, and
+// then cuts its buckets, while the piece's keys are expanded.
+static int staged_expand_chunks(fk_ctx *c, StreamWs on, hipStream_t cut, uint32_t nchunks,
+                                const std::vector<uint64_t> &bkm, double frac) {
+    hipStream_t s = on.s;
     const uint32_t p = c->st_np;
     uint64_t pk = 0, maxb = 0;
     for (uint64_t v : bkm) pk += v, maxb = std::max(maxb, v);
@@ -2340,13 +2443,12 @@ static int staged_expand_chunks(fk_ctx *c, uint32_t nchunks, const std::vector<u
     // piece 0.75 ms against 1.14 for a one-pass scatter)
     SortedPlan pl = c->st_plan;
     HIP_TRY(hipEventRecord(c->st_ev[4 * p + 2], s));
-    FK_TRY(sorted_expand(c, pl, nchunks, pk, c->st_keys[p], c->st_cb[p]));
+    FK_TRY(sorted_expand(c, on, cut, pl, nchunks, pk, c->st_keys[p], c->st_cb[p]));
     const uint64_t ncell_all = (uint64_t)c->nlb << c->st_plan.F;
     FK_TRY(ensure(c->st_total, ncell_all * 8));
-    if (c->cut_side) {  // the job's cell totals on the cut's stream, while this piece is expanded
-        HIP_TRY(hipStreamWaitEvent(c->tier_side, c->side_ev[2], 0));
-        HIP_TRY(launch_add_u64(c->st_total.as<uint64_t>(), c->cell_total.as<uint64_t>(), ncell_all, p == 0,
-                               c->tier_side));
+    if (cut) {  // the job's cell totals on the cut's stream, while this piece is expanded
+        HIP_TRY(hipStreamWaitEvent(cut, c->side_ev[2], 0));
+        HIP_TRY(launch_add_u64(c->st_total.as<uint64_t>(), c->cell_total.as<uint64_t>(), ncell_all, p == 0, cut));
     } else {
         HIP_TRY(launch_add_u64(c->st_total.as<uint64_t>(), c->cell_total.as<uint64_t>(), ncell_all, p == 0, s));
     }
@@ -2358,48 +2460,44 @@ static int staged_expand_chunks(fk_ctx *c, uint32_t nchunks, const std::vector<u
 }
 
 // One rank: partitions a piece of the mapped tiles by local bin, then expands it.
-static int staged_expand(fk_ctx *c, const RecSrc &src, double frac) {
+static int staged_expand(fk_ctx *c, StreamWs on, hipStream_t cut, const RecSrc &src, double frac) {
     const uint32_t p = c->st_np;
     if (p >= stage_maxp(c)) return set_err(FK_E_STATE, "more than %u staged pieces", stage_maxp(c));
     uint64_t nrecv = 0;
     std::vector<Chunk> chunks;
     std::vector<uint32_t> bcb;
     std::vector<uint64_t> bkm;
-    FK_TRY(partition_src(c, src, nrecv, chunks, bcb, bkm, c->st_ev[4 * p], c->st_ev[4 * p + 1]));
-    return staged_expand_chunks(c, (uint32_t)chunks.size(), bkm, frac);
+    FK_TRY(partition_src(c, on, src, nrecv, chunks, bcb, bkm, c->st_ev[4 * p], c->st_ev[4 * p + 1]));
+    return staged_expand_chunks(c, on, cut, (uint32_t)chunks.size(), bkm, frac);
 }
 
 // The job's count over the staged pieces: buckets over the summed cell totals, each bucket's keys
-// read from every piece (BucketSrc pieces), the dense result and its bin offsets.
-static int staged_count(fk_ctx *c) {
+// read from every piece (BucketSrc pieces), the dense result and its bin offsets.  `cut` (or null):
+// the side stream for the bucket cut, while the last piece is still being expanded on the main stream.
+static int staged_count(fk_ctx *c, hipStream_t cut) {
     const double t0 = now_ms();
-    hipStream_t s = c->stream;
+    const StreamWs on = c->main_on();
+    hipStream_t s = on.s;
     const SortedPlan pl = c->st_plan;
     const uint32_t nlb = c->nlb;
     const uint64_t ncell_all = (uint64_t)nlb << pl.F;
     HIP_TRY(hipEventRecord(c->ev[6], s));
     std::swap(c->cell_total, c->st_total);  // the job's cell totals (st_total is rebuilt by the next job)
     FK_TRY(ensure(c->cell_base, (ncell_all + 1) * 8));
-    // the bucket cut (this scan, sorted_count_buckets' flags, buckets and tiers) on the cut's stream when
-    // the last piece is still being expanded on `s` (cut_side)
-    const hipStream_t cs = c->cut_side ? c->tier_side : s;
-    if (cs != s) HIP_TRY(hipStreamWaitEvent(cs, c->side_ev[2], 0));
+    // the bucket cut (this scan, then bucket_cut's flags, buckets and tiers) on the cut's stream
+    const hipStream_t cs = cut ? cut : s;
+    if (cut) HIP_TRY(hipStreamWaitEvent(cut, c->side_ev[2], 0));
     HIP_TRY(scan_excl_sum_u64(c->cell_total.as<uint64_t>(), c->cell_base.as<uint64_t>(), ncell_all,
-                              c->cell_base.as<uint64_t>() + ncell_all, c->ws, cs));
+                              c->cell_base.as<uint64_t>() + ncell_all, *on.ws, cs));
     BucketSrc src{nullptr, pl.F};
     src.np = (int)c->st_np;
     for (uint32_t p = 0; p < c->st_np; ++p) {
         src.pk[p] = c->st_keys[p].as<uint64_t>();
         src.pcb[p] = c->st_cb[p].as<uint64_t>();
     }
-    FK_TRY(sorted_count(c, pl, src, c->st_kmers));
+    FK_TRY(sorted_count(c, on, cut, pl, src, c->st_kmers));
     HIP_TRY(hipEventRecord(c->ev[7], s));
-    c->h_bin_off.assign((size_t)nlb + 1, 0);
-    if (c->pin_down.ensure(((size_t)nlb + 1) * 8)) return set_err(FK_E_NOMEM, "hipHostMalloc failed");
-    HIP_TRY(hipMemcpyAsync(c->pin_down.p, c->bin_off.p, ((uint64_t)nlb + 1) * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    memcpy(c->h_bin_off.data(), c->pin_down.p, ((size_t)nlb + 1) * 8);
-    resolve_distinct(c);
+    FK_TRY(read_bin_offsets(c, s));
     htrace("staged: bin offsets read");
     double mp = 0.0, mx = 0.0;
     for (uint32_t p = 0; p < c->st_np; ++p) {
@@ -2409,10 +2507,7 @@ static int staged_count(fk_ctx *c) {
     c->stats.ms_partition = mp;
     c->stats.ms_count = mx + ev_ms(c->ev[6], c->ev[7]);
     c->stats.pieces_counted = c->st_np;
-    c->stats.records_received = c->nrec;
-    c->stats.distinct = c->distinct;
-    c->stats.ms_total += now_ms() - t0;
-    c->have_result = true;
+    count_done(c, c->nrec, t0);
     return FK_OK;
 }
 
@@ -2424,10 +2519,7 @@ static int staged_count(fk_ctx *c) {
 // size: every piece_bytes, at most three pieces before fk_finish stages the last one (with cuts: at
 // most stage_maxp - 1).
 static bool local_piece_due(const fk_ctx *c, uint64_t tiles) {
-#ifndef FK_MIN_PIECE_MB
-#define FK_MIN_PIECE_MB 256  // A/B builds: a piece holds >= half of it
-#endif
-    constexpr uint64_t MIN_PIECE = (uint64_t)FK_MIN_PIECE_MB << 20;
+    constexpr uint64_t MIN_PIECE = 256ull << 20;  // a piece holds >= half of it
     if (c->st_np >= stage_maxp(c) - 1) return false;
     const uint64_t tile = fm_tile_bytes(FUSED_NT);
     if (c->job_bytes && !c->piece_bytes_set) {
@@ -2440,26 +2532,12 @@ static bool local_piece_due(const fk_ctx *c, uint64_t tiles) {
     return c->st_np < 3 && (tiles - c->tiles_counted) * tile >= c->piece_bytes;
 }
 
-// The context's stream and scan workspace swapped for the staging stream's while a staging step is
-// queued (the expansion code queues on c->stream).
-struct StageStream {
-    fk_ctx *c;
-    explicit StageStream(fk_ctx *c_) : c(c_) {
-        std::swap(c->stream, c->xstage);
-        std::swap(c->ws, c->ws_x);
-    }
-    ~StageStream() {
-        std::swap(c->stream, c->xstage);
-        std::swap(c->ws, c->ws_x);
-    }
-};
-
 // tiles: the tiles mapped once `mapped` (recorded on the map stream) has passed.  The piece is
-// partitioned and expanded on the staging stream (StageStream), which fk_finish joins (xstage_ev).
+// partitioned and expanded on the staging stream, which fk_finish joins (xstage_ev).
 static int local_maybe_piece(fk_ctx *c, uint64_t tiles, hipEvent_t mapped) {
     if (!staged_eligible(c) || c->pieces_void || !local_piece_due(c, tiles)) return FK_OK;
-    StageStream ss_(c);
-    hipStream_t s = c->stream;  // the staging stream
+    const StreamWs on = c->stage_on();
+    hipStream_t s = on.s;
     HIP_TRY(hipStreamWaitEvent(s, mapped, 0));
     uint64_t h[4] = {0, 0, 0, 0};
     HIP_TRY(hipMemcpyAsync(h, c->counters.p, 32, hipMemcpyDeviceToHost, s));
@@ -2472,7 +2550,8 @@ static int local_maybe_piece(fk_ctx *c, uint64_t tiles, hipEvent_t mapped) {
     const RecSrc src = fused_src(c, t0, nt, nt * map_fused_tcap());
     c->tiles_counted = tiles;
     c->st_cut += 1;
-    FK_TRY(staged_expand(c, src, c->job_bytes ? (double)(nt * fm_tile_bytes(FUSED_NT)) / (double)c->job_bytes : 0.0));
+    FK_TRY(staged_expand(c, on, nullptr, src,
+                         c->job_bytes ? (double)(nt * fm_tile_bytes(FUSED_NT)) / (double)c->job_bytes : 0.0));
     HIP_TRY(hipEventRecord(c->xstage_ev, s));
     return FK_OK;
 }
@@ -2708,8 +2787,8 @@ static int xch_stage_segments(fk_ctx *c, size_t s1, double frac) {
     if (s1 <= c->segs_counted) return FK_OK;
     const uint32_t p = c->st_np;
     if (p >= stage_maxp(c)) return set_err(FK_E_STATE, "more than %u staged pieces", stage_maxp(c));
-    StageStream ss_(c);
-    hipStream_t s = c->stream;  // the staging stream
+    const StreamWs on = c->stage_on();
+    hipStream_t s = on.s;
     // its earlier work (behind earlier steps' transfers) is done: bounded with a communicator
     FK_TRY(comm_sync(c, s));
     const uint64_t step = c->xch.segs[s1 - 1].step;
@@ -2723,10 +2802,10 @@ static int xch_stage_segments(fk_ctx *c, size_t s1, double frac) {
     std::vector<uint32_t> bcb;
     build_chunks(c->nlb, ranges, chunks, bcb);
     HIP_TRY(hipEventRecord(c->st_ev[4 * p], s));
-    FK_TRY(upload_chunks(c, chunks, bcb));
+    FK_TRY(upload_chunks(c, s, chunks, bcb));
     HIP_TRY(hipEventRecord(c->st_ev[4 * p + 1], s));
     c->rsrc = c->xrecv.as<uint64_t>();
-    return staged_expand_chunks(c, (uint32_t)chunks.size(), bkm, frac);
+    return staged_expand_chunks(c, on, nullptr, (uint32_t)chunks.size(), bkm, frac);
 }
 
 // Received records of this job so far / expected in all (estimated from the share of the input
@@ -2825,7 +2904,7 @@ static int finish_exchange(fk_ctx *c) {
             HIP_TRY(hipEventRecord(c->xstage_ev, c->xstage));
             HIP_TRY(hipStreamWaitEvent(s, c->xstage_ev, 0));
         }
-        FK_TRY(staged_count(c));
+        FK_TRY(staged_count(c, nullptr));
     } else {
         std::vector<std::vector<std::pair<uint64_t, uint64_t>>> ranges;
         std::vector<uint64_t> bkm;
@@ -2867,24 +2946,20 @@ static int finish_local(fk_ctx *c) {
     DeviceGuard dg_(c->device);
     if (c->st_np && c->rec_tiled && !c->pieces_void && c->tiles_counted <= c->rec_tiles) {
         // staged pieces were expanded while the input landed: the last piece, then one count
-#ifndef FK_CUT_SIDE
-#define FK_CUT_SIDE 1  // A/B builds: -DFK_CUT_SIDE=0 the bucket cut after the last piece's expansion
-#endif
         // the job's bucket cut needs the last piece's cell totals, not its keys: it runs on the side
         // stream while the piece's two expansion levels run on `stream`
         int rc = FK_OK;
-        c->cut_side = FK_CUT_SIDE && c->tier_side && c->rec_tiles > c->tiles_counted;
+        const hipStream_t cut = c->rec_tiles > c->tiles_counted ? c->tier_side : nullptr;
         // the cut's stream starts after everything queued so far (re-recorded once the last piece's cell
         // offsets are scanned; a piece without k-mers records nothing more)
-        if (c->cut_side) HIP_TRY(hipEventRecord(c->side_ev[2], c->stream));
+        if (cut) HIP_TRY(hipEventRecord(c->side_ev[2], c->stream));
         if (c->rec_tiles > c->tiles_counted) {
             const uint64_t t0 = c->tiles_counted, nt = c->rec_tiles - t0;
-            rc = staged_expand(c, fused_src(c, t0, nt, nt * map_fused_tcap()),
+            rc = staged_expand(c, c->main_on(), cut, fused_src(c, t0, nt, nt * map_fused_tcap()),
                                c->job_bytes ? (double)(nt * fm_tile_bytes(FUSED_NT)) / (double)c->job_bytes : 0.0);
         }
-        if (rc == FK_OK) rc = staged_count(c);
-        if (c->cut_side) (void)hipStreamSynchronize(c->tier_side);
-        c->cut_side = false;
+        if (rc == FK_OK) rc = staged_count(c, cut);
+        if (cut) (void)hipStreamSynchronize(cut);
         FK_TRY(rc);
         pieces_reset(c);
         return FK_OK;

@@ -546,25 +546,6 @@ __device__ __forceinline__ const uint64_t *bucket_key_ptr(const BucketView &v, u
     return reinterpret_cast<const uint64_t *>(a);
 }
 
-
-// key i of a bucket whose row of 64 keys starts at row0 (i = row0 + lane): when the whole row lies in
-// one piece (most rows: a piece holds ~n / np of the bucket's keys) its base is picked by scalar
-// compares and the lane adds its offset; a row across a piece boundary takes bucket_key_ptr's
-// per-lane selects (~20 VALU per key); no vector registers held between rows (the mid tier's key-range
-// kernel, whose passes over its rows surround its counts: -DFK_PARTS_RB=0)
-template <int KW = 1>
-__device__ __forceinline__ const uint64_t *bucket_row_key_ptr(const BucketView &v, uint32_t row0, uint32_t i) {
-    bool one = true;  // uniform: no boundary inside the row
-    uintptr_t a = (uintptr_t)v.b[0];
-#pragma unroll
-    for (int q = 1; q < stage_npc<KW>(); ++q) {
-        one = one && (row0 >= v.p[q] || row0 + 63u < v.p[q]);
-        a += row0 >= v.p[q] ? (uintptr_t)v.b[q] - (uintptr_t)v.b[q - 1] : 0;  // as bucket_key_ptr, uniform
-    }
-    if (one) return reinterpret_cast<const uint64_t *>(a + (uintptr_t)i * (8u * KW));
-    return bucket_key_ptr<KW>(v, i);
-}
-
 // A bucket's rows of 64 keys, 64 rows at a time: lane r works out row r's piece base once (the
 // compares run on the lanes together, not per row on the scalar unit: ~25 scalar instructions per row
 // before) and whether a piece boundary falls inside the row; a row then takes its base with two lane
@@ -934,11 +915,8 @@ __global__ __launch_bounds__(NT) void k_bucket_count64(BucketSrc src, const Buck
 // 15.4 ms for the 58 K such buckets of a configs[2] per-GPU load), any number of keys with at
 // most BIG_HC distinct; the others keep bucket_unique = REDO (the streaming path) and count into
 // *oversize
-#ifndef FK_BIG_HC
-#define FK_BIG_HC 4096  // A/B builds: -DFK_BIG_HC=3072 -DFK_BIG_HS=5120 (52 KB: three workgroups per CU)
-#define FK_BIG_HS 6144
-#endif
-constexpr uint32_t BIG_HC = FK_BIG_HC, BIG_HS = FK_BIG_HS;
+// (3072 / 5120 slots, 52 KB, three workgroups per CU: profiles/r04c_big_tier_5120_ab.txt)
+constexpr uint32_t BIG_HC = 4096, BIG_HS = 6144;
 hipError_t launch_bucket_count64_big(const BucketSrc &src, const Bucket *buckets, uint64_t nlist, int k,
                                      uint64_t *out_keys, uint32_t *out_counts, uint64_t *bucket_unique,
                                      unsigned long long *oversize, const uint32_t *list, hipStream_t s) {
@@ -1207,9 +1185,6 @@ __device__ __forceinline__ void wave_rank64(unsigned long long *s_gk, uint16_t *
 // (the mid tier's up to 1024 keys on the 512-key table): the count gives up -- returns ~0u, writes
 // nothing -- once more than CAP distinct keys appear (checked before each row: the table keeps
 // SL - CAP >= 64 free slots for the row's new keys).
-#ifndef FK_W64_CAS
-#define FK_W64_CAS 1  // A/B builds: -DFK_W64_CAS=0 the first probes read together, swaps only on empty slots
-#endif
 template <uint32_t CAP, uint32_t SL, bool ORD = true, int WKPT = WaveCfg<CAP>::KPT, int NROW = WKPT>
 __device__ __forceinline__ uint32_t wave_count_keys(WaveLds<CAP, SL> &w, uint64_t begin, uint32_t n, uint64_t lo,
                                                 int span_bits, uint64_t q, const uint64_t (&kk)[NROW],
@@ -1236,8 +1211,8 @@ __device__ __forceinline__ uint32_t wave_count_keys(WaveLds<CAP, SL> &w, uint64_
     wave_lds_sync();
     // 1. dedupe: the lane's keys are inserted one after another, every probe a
     //    compare-and-swap (an occupied slot returns its key: one LDS round trip
-    //    per probe and a short loop; FK_W64_CAS=0 keeps round 5's form, the
-    //    first probes read together and a swap only on an empty slot -- slower
+    //    per probe and a short loop; round 5's form, the first probes
+    //    read together and a swap only on an empty slot, was slower
     //    at every load measured: configs[2] wave tier 24.2 -> 21.4 ms, configs[1]
     //    step 22.3 -> 22.1 ms, profiles/r06i_ab.txt).  The list of new keys'
     //    slots is built from ballots (the wave owns the bucket: no atomic
@@ -1246,11 +1221,6 @@ __device__ __forceinline__ uint32_t wave_count_keys(WaveLds<CAP, SL> &w, uint64_
     uint32_t sl[NROW];
 #pragma unroll
     for (int j = 0; j < NROW; ++j) sl[j] = wslot<SL>(kk[j]);
-#if FK_W64_CAS == 0
-    unsigned long long old[NROW];
-#pragma unroll
-    for (int j = 0; j < NROW; ++j) old[j] = s_k[sl[j]];
-#endif
     uint32_t U = 0;
 #pragma unroll
     for (int j = 0; j < NROW; ++j) {
@@ -1260,25 +1230,12 @@ __device__ __forceinline__ uint32_t wave_count_keys(WaveLds<CAP, SL> &w, uint64_
         bool fresh = false;
         if (key != EMPTY_KEY) {
             uint32_t s = sl[j];
-#if FK_W64_CAS
-            for (;;) {  // every probe a compare-and-swap (FK_W64_CAS)
+            for (;;) {  // every probe a compare-and-swap
                 const unsigned long long prev = atomicCAS(&s_k[s], EMPTY_KEY, (unsigned long long)key);
                 fresh = prev == EMPTY_KEY;
                 if (fresh || prev == key) break;
                 s = s + 1 == SL ? 0u : s + 1;
             }
-#else
-            unsigned long long cur = old[j];
-            for (;;) {
-                if (cur == EMPTY_KEY) {
-                    cur = atomicCAS(&s_k[s], EMPTY_KEY, (unsigned long long)key);
-                    fresh = cur == EMPTY_KEY;
-                }
-                if (fresh || cur == key) break;
-                s = s + 1 == SL ? 0u : s + 1;
-                cur = s_k[s];
-            }
-#endif
             atomicAdd(reinterpret_cast<uint32_t *>(&s_c[s & ~1u]), 1u << (16 * (s & 1u)));
             sl[j] = s;
         }
@@ -1586,20 +1543,11 @@ __global__ __launch_bounds__(64) void k_bucket_count64_parts(BucketSrc src, cons
     else v = bucket_view(src, b);
     const uint32_t n = b.n;
     const uint64_t *klast = bucket_key_ptr(v, n - 1);
-#ifndef FK_PARTS_RB
-#define FK_PARTS_RB 1  // A/B builds: -DFK_PARTS_RB=0 each row's base from scalar compares (no registers held)
-#endif
-#if FK_PARTS_RB
     const RowBases rb = row_bases(v);  // the 16 rows' piece bases, once
     auto key_at = [&](uint32_t row0, uint32_t i) {
         const uint64_t *pa = row_key_ptr(v, rb, (int)(row0 >> 6), i);
         return ldg_nt<uint64_t>(i < n ? pa : klast);
     };
-#else
-    auto key_at = [&](uint32_t row0, uint32_t i) {
-        return ldg_nt<uint64_t>(i < n ? bucket_row_key_ptr(v, row0, i) : klast);
-    };
-#endif
     // 1. a sample of 64 keys, one per lane, sorted across the wave (bitonic, ascending by lane)
     unsigned long long x = *bucket_key_ptr(v, (uint32_t)(((uint64_t)lane * n) >> 6));
 #pragma unroll
@@ -1618,26 +1566,16 @@ __global__ __launch_bounds__(64) void k_bucket_count64_parts(BucketSrc src, cons
     auto range_of = [&](unsigned long long key) -> uint32_t {
         return (key > sp0 ? 1u : 0u) + (P == 3 && key > sp1 ? 1u : 0u);
     };
-#ifndef FK_PARTS_REG
-#define FK_PARTS_REG 1  // A/B builds: -DFK_PARTS_REG=0 the keys read again (from L2) by every pass below
-#endif
-#if FK_PARTS_REG
     // the bucket's keys in registers (16 per lane), read once for the size pass and every gather
     uint64_t kr[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) kr[r] = key_at(r * 64, r * 64 + lane);
-#define FK_PARTS_KEY(r_) kr[r_]
-#define FK_PARTS_UNROLL _Pragma("unroll")
-#else
-#define FK_PARTS_KEY(r_) key_at((r_) * 64, (r_) * 64 + lane)
-#define FK_PARTS_UNROLL _Pragma("unroll 4")
-#endif
     // 3. the ranges' sizes; one above the wave tier's cap leaves the bucket to the 1024-key kernel
     uint32_t c0 = 0, c1 = 0;
-    FK_PARTS_UNROLL
+#pragma unroll
     for (int r = 0; r < R; ++r) {
         const uint32_t i = r * 64 + lane;
-        const unsigned long long key = FK_PARTS_KEY(r);
+        const unsigned long long key = kr[r];
         const uint32_t g = range_of(key);
         c0 += (i < n && g == 0) ? 1u : 0u;
         c1 += (i < n && g == 1) ? 1u : 0u;
@@ -1656,10 +1594,10 @@ __global__ __launch_bounds__(64) void k_bucket_count64_parts(BucketSrc src, cons
     for (uint32_t g = 0; g < P; ++g) {
         const uint32_t ng = g == 0 ? n0 : g == 1 ? n1 : n2;
         uint32_t at = 0;
-        FK_PARTS_UNROLL
+    #pragma unroll
         for (int r = 0; r < R; ++r) {
             const uint32_t i = r * 64 + lane;
-            const unsigned long long key = FK_PARTS_KEY(r);
+            const unsigned long long key = kr[r];
             const bool mine = i < n && range_of(key) == g;
             const uint64_t m = __ballot(mine);
             if (mine)
@@ -1680,8 +1618,6 @@ __global__ __launch_bounds__(64) void k_bucket_count64_parts(BucketSrc src, cons
         pre += wave_count_keys<CAP, SL, ORD>(w, b.begin + pre, ng, lo, span, 0, kk, out_keys, out_counts, nullptr);
     }
     if (lane == 0) bucket_unique[q] = pre;
-#undef FK_PARTS_KEY
-#undef FK_PARTS_UNROLL
 }
 
 hipError_t launch_bucket_count64_parts(const BucketSrc &src, const Bucket *buckets, const uint32_t *list,
@@ -1771,10 +1707,7 @@ hipError_t launch_bucket_count64_mid512(const BucketSrc &src, const Bucket *buck
 //      configs[2] load, profiles/r05x_sub_seq_ab.txt).  A bucket with a sub-bucket above 512 keys (a
 //      k-mer repeated that often) keeps the block / big-table path.
 // ---------------------------------------------------------------------------
-#ifndef FK_SPL_TGT
-#define FK_SPL_TGT 256  // A/B builds: -DFK_SPL_TGT=n the split's target keys per sub-bucket
-#endif
-constexpr uint32_t SPL_TGT = FK_SPL_TGT;  // target keys per sub-bucket (the wave tier takes up to 512)
+constexpr uint32_t SPL_TGT = 256;  // target keys per sub-bucket (the wave tier takes up to 512)
 constexpr uint32_t SPL_OVER = 16;     // samples per sub-bucket
 
 // a split bucket's room in the split copy: slots = true (64-bit keys), a SPL_SLOT-key region per
@@ -2358,7 +2291,7 @@ __device__ __forceinline__ uint32_t wave_count_keys128(WaveLds128<CAP, SL> &w, u
     return U;
 }
 
-// ---- the 128-bit wave tier with a fingerprint table (FK_W128_FP, the default).  The uniform-round
+// ---- the main 128-bit wave tier, with a fingerprint table.  The uniform-round
 // dedupe above waits on every probe round twice (the hi-word claim, then the lo word of a matching
 // slot).  Here the table holds a 64-bit fingerprint of each key: a probe is one compare-and-swap or
 // read per round, lanes probe independently (the 64-bit tier's loop), and with 2 * CAP slots the table
@@ -2426,9 +2359,6 @@ __device__ __forceinline__ uint32_t wave_count_exact128(const unsigned long long
     return (uint32_t)__shfl((int)wave_incl_sum<uint32_t>(u), 63, 64);
 }
 
-#ifndef FK_W128_CAS
-#define FK_W128_CAS 1  // A/B builds: -DFK_W128_CAS=0 the first probes read together, swaps only on empty slots
-#endif
 template <uint32_t CAP, bool ORD = true, int W2KPT = CAP / 64>
 __device__ __forceinline__ uint32_t wave_count_keys128_fp(WaveLdsFp<CAP> &w, uint64_t begin, uint32_t n, u128 lo_b,
                                                       int span_bits, uint64_t q, const uint64_t (&khi)[W2KPT],
@@ -2450,7 +2380,7 @@ __device__ __forceinline__ uint32_t wave_count_keys128_fp(WaveLdsFp<CAP> &w, uin
         for (uint32_t s = lane; s < SL / 4; s += 64) c4[s] = make_uint4(0, 0, 0, 0);
     }
     wave_lds_sync();
-    // 1. dedupe on fingerprints: first probes read together, then the 64-bit tier's per-lane loop
+    // 1. dedupe on fingerprints, with the 64-bit tier's per-lane loop
     uint64_t fp[W2KPT];
     uint32_t sl[W2KPT], cidx[W2KPT];
 #pragma unroll
@@ -2459,11 +2389,6 @@ __device__ __forceinline__ uint32_t wave_count_keys128_fp(WaveLdsFp<CAP> &w, uin
         sl[j] = wslot<SL>(fp[j]);
     }
     static_assert((SL & (SL - 1)) == 0, "probe wrap by mask");
-#if FK_W128_CAS == 0
-    unsigned long long old[W2KPT];
-#pragma unroll
-    for (int j = 0; j < W2KPT; ++j) old[j] = w.f[sl[j]];
-#endif
     uint32_t U = 0;
 #pragma unroll
     for (int j = 0; j < W2KPT; ++j) {
@@ -2471,7 +2396,6 @@ __device__ __forceinline__ uint32_t wave_count_keys128_fp(WaveLdsFp<CAP> &w, uin
         bool fresh = false;
         uint32_t s = sl[j];
         if (key != EMPTY_KEY) {
-#if FK_W128_CAS
             // every probe a compare-and-swap: an occupied slot returns its fingerprint, so a fresh key
             // takes one LDS round trip at its home slot instead of a read and then the swap (most keys
             // of a 128-bit bucket are distinct); 29.0 against 30.5 ms per configs[3]-load launch
@@ -2481,18 +2405,6 @@ __device__ __forceinline__ uint32_t wave_count_keys128_fp(WaveLdsFp<CAP> &w, uin
                 if (fresh || prev == key) break;
                 s = (s + 1) & (SL - 1);
             }
-#else
-            unsigned long long cur = old[j];
-            for (;;) {
-                if (cur == EMPTY_KEY) {
-                    cur = atomicCAS(&w.f[s], EMPTY_KEY, (unsigned long long)key);
-                    fresh = cur == EMPTY_KEY;
-                }
-                if (fresh || cur == key) break;
-                s = (s + 1) & (SL - 1);
-                cur = w.f[s];
-            }
-#endif
             sl[j] = s;
         }
         const uint64_t m = __ballot(fresh);
@@ -2581,9 +2493,6 @@ __device__ __forceinline__ void wave_count_bucket128(WaveLds128<CAP, SL> &w, con
 }
 
 // list: bucket indices (the mid tier: buckets of CAP / 2 < n <= CAP keys), or null for every bucket
-#ifndef FK_W128_FP
-#define FK_W128_FP 1  // A/B builds: -DFK_W128_FP=0 the uniform-round dedupe in every 128-bit wave tier
-#endif
 template <int BPW, uint32_t SL, bool MS = false, uint32_t CAP = W2CAP, bool ORD = true, bool FP = false>
 __global__ __launch_bounds__(64) void k_bucket_count128_wave(BucketSrc src,
                                                              const Bucket *__restrict__ buckets, uint64_t nbuckets,
@@ -2693,7 +2602,7 @@ hipError_t launch_bucket_count128_wave(const BucketSrc &src, const Bucket *bucke
     if (k > 63 || k <= 32) return hipErrorInvalidValue;
     const unsigned g = (unsigned)((nbuckets + 1) / 2);
 #define FK_W128(MS, ORD)                                                                                   \
-    k_bucket_count128_wave<2, W2CAP * 3 / 2, MS, W2CAP, ORD, (FK_W128_FP != 0)><<<g, 64, 0, s>>>(       \
+    k_bucket_count128_wave<2, W2CAP * 3 / 2, MS, W2CAP, ORD, true><<<g, 64, 0, s>>>(                   \
         src, buckets, nbuckets, k, out_keys, out_counts, bucket_unique)
     if (src.np > 0 && ordered)
         FK_W128(true, true);

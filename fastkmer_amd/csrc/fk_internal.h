@@ -44,10 +44,7 @@ struct Bucket {
 // the staged pieces' key arrays (one job's input expanded piece by piece while it landed, and
 // counted once): piece p holds the bucket's keys at pk[p][pcb[p][g0] .. pcb[p][g1]), g0 / g1 =
 // (lbin << F) + c0 / c1, pcb[p] the exclusive scan of the piece's cell totals.
-#ifndef FK_STAGE_MAXP
-#define FK_STAGE_MAXP 5
-#endif
-constexpr int STAGE_MAXP = FK_STAGE_MAXP;
+constexpr int STAGE_MAXP = 5;
 static_assert(STAGE_MAXP >= 4 && STAGE_MAXP <= 8, "staged pieces per job");
 // 128-bit keys (k > 32) stage at most 4 pieces: their kernels' piece loops stop there (a fifth
 // piece's bounds cost configs[3] 0.5-0.9 ms per step, profiles/r06z_five_pieces.txt)
@@ -203,17 +200,13 @@ hipError_t launch_bucket_count64_big(const BucketSrc &src, const Bucket *buckets
                                      uint64_t *out_keys, uint32_t *out_counts, uint64_t *bucket_unique,
                                      unsigned long long *oversize, const uint32_t *list, hipStream_t s);
 constexpr uint32_t WAVE_BUCKET_CAP = 512;
-#ifndef FK_WAVE_SL
-#define FK_WAVE_SL 640  // table slots of a 512-key wave bucket (7.4 KB of LDS per wave, 6 waves per SIMD; 768:
-                        // 5, 1.4 ms slower at the configs[2] load, profiles/r05l_wave_slots_ab.txt)
-#endif
-constexpr uint32_t WAVE_SLOTS = FK_WAVE_SL;
+// table slots of a 512-key wave bucket (7.4 KB of LDS per wave, 6 waves per SIMD; 768: 5, 1.4 ms
+// slower at the configs[2] load, profiles/r05l_wave_slots_ab.txt)
+constexpr uint32_t WAVE_SLOTS = 640;
 constexpr uint32_t WAVE_MID_CAP = 1024;  // 64-bit mid wave tier: listed buckets of 513 .. 1024 keys
-#ifndef FK_MID_SL
-#define FK_MID_SL 1280  // its table slots (14.6 KB per wave; 1536: kernel 2.15 vs 2.03 ms at the configs[2]
-                        // load, profiles/r05q_mid_slots_ab.txt)
-#endif
-constexpr uint32_t WAVE_MID_SLOTS = FK_MID_SL;
+// its table slots (14.6 KB per wave; 1536: kernel 2.15 vs 2.03 ms at the configs[2] load,
+// profiles/r05q_mid_slots_ab.txt)
+constexpr uint32_t WAVE_MID_SLOTS = 1280;
 constexpr uint32_t WAVE128_BUCKET_CAP = 256;  // keys per wave-tier bucket, 128-bit keys (k_bucket_count128_wave)
 hipError_t launch_bucket_count128_wave(const BucketSrc &src, const Bucket *buckets, uint64_t nbuckets, int k,
                                        uint64_t *out_keys, uint32_t *out_counts, uint64_t *bucket_unique,

@@ -185,9 +185,6 @@ __device__ __forceinline__ void fm_norm_block(const uint32_t *s_codes, int blk, 
     }
 }
 
-#ifndef FK_MAPV
-#define FK_MAPV 4  // A/B builds: -DFK_MAPV=1 / 2 / 3 the previous formulations
-#endif
 // acc * 2 + (a != b): the compare's lane mask is the carry-in of the add
 __device__ __forceinline__ uint32_t fm_push_ne(uint32_t acc, uint32_t a, uint32_t b) {
     uint32_t r;
@@ -230,9 +227,6 @@ __global__ __launch_bounds__(NTH) void k_map_fused(const uint8_t *__restrict__ f
     __shared__ uint32_t s_wnk[NTH / 64], s_wovf, s_tcnt;
     __shared__ uint64_t s_bcast[2];
     __shared__ uint32_t s_pown, s_pall;
-#if FK_MAPV < 3
-    __shared__ uint8_t s_first[NTH];  // the thread's first byte is '>'
-#endif
 
 #ifdef FK_PROBES
     unsigned long long fm_t0 = fm_stamp(), fm_acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -251,7 +245,7 @@ __global__ __launch_bounds__(NTH) void k_map_fused(const uint8_t *__restrict__ f
         }
     };
     // The tile's input registers: the thread's 64 bytes; wave 0 also the first 1 KB read-back
-    // window before the tile (line state, below), thread 0 the input's first byte and (FK_MAPV 3)
+    // window before the tile (line state, below), thread 0 the input's first byte and
     // the wave's last lane the first byte of the next thread's 64 (a line starting there is a
     // header iff it is '>'; the other lanes take it by a lane shift), all issued together so that
     // their latencies overlap
@@ -263,7 +257,7 @@ __global__ __launch_bounds__(NTH) void k_map_fused(const uint8_t *__restrict__ f
         rb0[0] = rb0[1] = rb0[2] = rb0[3] = 0u;
         if (tid < 64 && t0_ >= 1024) load_rb(t0_ - 1024 + 16 * (uint64_t)tid, rb0);
         fa_first = (tid == 0 && t0_ > 0) ? (uint32_t)fa[0] : (uint32_t)'>';
-        const bool last_lane = FK_MAPV >= 3 && (tid & 63) == 63 && tid + 1 < NTH && p0_ + 64 < n;
+        const bool last_lane = (tid & 63) == 63 && tid + 1 < NTH && p0_ + 64 < n;
         next_byte = last_lane ? (uint32_t)fa[p0_ + 64] : 0u;
     };
     {
@@ -344,19 +338,13 @@ __global__ __launch_bounds__(NTH) void k_map_fused(const uint8_t *__restrict__ f
     // header ('>' first); the exclusive block max gives the line holding p0.  The tile's initial
     // value comes from reading back to the last newline before t0 (wave 0, 1 KB a step).
     // A line that starts at the next thread's first byte (newline at byte 63) is a header iff that
-    // byte is '>': the threads publish their first byte's class in LDS.  Line starts are held
+    // byte is '>': the lanes take their successor's first-byte class by a lane shift (the wave's last
+    // lane from the byte it loaded).  Line starts are held
     // tile-relative (+ FM_LS_BIAS, so the read-back range stays positive) in 32-bit values; 0 = none.
-#if FK_MAPV >= 3
     const uint32_t my_first = (uint32_t)(gt & 1ull);
     const uint32_t nxt_first = (tid & 63) == 63 ? (next_byte == '>' ? 1u : 0u)
                                                 : dpp32<0x130, 0xf>(0u, my_first);  // wave_shl:1
     const uint32_t tile_first = (uint32_t)__builtin_amdgcn_readlane((int)my_first, 0);  // wave 0: thread 0
-#else
-    s_first[tid] = (uint8_t)(gt & 1ull);
-    __syncthreads();
-    const uint32_t nxt_first = tid + 1 < NTH ? (uint32_t)s_first[tid + 1] : 0u;
-    const uint32_t tile_first = s_first[0];
-#endif
     uint32_t val = 0u;
     if (nl) {
         const int ql = 63 - __clzll(nl);
@@ -410,8 +398,8 @@ __global__ __launch_bounds__(NTH) void k_map_fused(const uint8_t *__restrict__ f
         }
     }
     uint32_t tile_last;
-    // (no trailing barrier from FK_MAPV 3: s_tmp32 is not written again)
-    const uint32_t excl = block_excl_max<uint32_t, (FK_MAPV < 3), NTH>(val, 0u, s_tmp32, &tile_last);
+    // (no trailing barrier: s_tmp32 is not written again)
+    const uint32_t excl = block_excl_max<uint32_t, false, NTH>(val, 0u, s_tmp32, &tile_last);
     const uint32_t prev = max(excl, (uint32_t)s_bcast[0]);
     const uint64_t ls = t0 + (prev >> 1) - FM_LS_BIAS;
     const bool ls0 = nb > 0 && ls == p0;
@@ -438,9 +426,9 @@ __global__ __launch_bounds__(NTH) void k_map_fused(const uint8_t *__restrict__ f
         return;
     }
 
-    // ---- 2. compaction into tile-local LDS streams (LSB-first), then MSB-first in place.  Each
-    // 32-byte half is compacted run by run on 64-bit code words, then the halves are joined.
-    const uint32_t my_off = block_excl_sum<uint32_t, (FK_MAPV < 3), NTH>((uint32_t)__popcll(kept), s_sum, &P_all);
+    // ---- 2. compaction into tile-local LDS streams (MSB-first).  Each 32-byte half is compacted
+    // run by run on 64-bit code words (LSB-first), then the halves are joined.
+    const uint32_t my_off = block_excl_sum<uint32_t, false, NTH>((uint32_t)__popcll(kept), s_sum, &P_all);
     if (tid == NTH - FM_HALO_T) s_pown = my_off;
     {
         uint64_t alo = 0, ahi = 0;
@@ -458,14 +446,13 @@ __global__ __launch_bounds__(NTH) void k_map_fused(const uint8_t *__restrict__ f
             const uint32_t hi = sh ? (uint32_t)(acc >> (128 - sh)) : 0u;
             const int nw = (sh + 2 * na + 31) >> 5;
             uint32_t *dst = &s_code[my_off >> 4];
-            // FK_MAPV 3: each partial word turned MSB-first before it is ORed in (a bit permutation
-            // commutes with OR), so no in-place reversal pass and its barrier
+            // each partial word is turned MSB-first before it is ORed in (a bit permutation commutes
+            // with OR), so there is no in-place reversal pass and no barrier for it
             auto msb_codes = [](uint32_t x) {
-                if (FK_MAPV < 3) return x;
                 x = __builtin_bitreverse32(x);
                 return ((x >> 1) & 0x55555555u) | ((x & 0x55555555u) << 1);
             };
-            auto msb_valid = [](uint32_t x) { return FK_MAPV < 3 ? x : __builtin_bitreverse32(x); };
+            auto msb_valid = [](uint32_t x) { return __builtin_bitreverse32(x); };
 #pragma unroll
             for (int j = 0; j < 5; ++j)
                 if (j < nw) atomicOr(&dst[j], msb_codes(j < 4 ? (uint32_t)(lo >> (32 * j)) : hi));
@@ -480,15 +467,7 @@ __global__ __launch_bounds__(NTH) void k_map_fused(const uint8_t *__restrict__ f
         }
     }
     __syncthreads();
-#if FK_MAPV < 3
-    for (int i = tid; i < Gm::CODE_WORDS; i += NTH) {
-        uint32_t x = __builtin_bitreverse32(s_code[i]);
-        s_code[i] = ((x >> 1) & 0x55555555u) | ((x & 0x55555555u) << 1);
-    }
-    for (int i = tid; i < Gm::VALID_WORDS; i += NTH) s_valid[i] = __builtin_bitreverse32(s_valid[i]);
-    __syncthreads();
-#endif
-    FM_STAMP(2);  // compaction into LDS + MSB-first reversal
+    FM_STAMP(2);  // compaction into LDS (MSB-first)
     if (probe == 2) {  // stop after the compaction
         if (s_code[tid] == 0x01234567u && s_valid[tid & 63] == 0x89abcdefu) counters[6] = tid;
         return;
@@ -546,8 +525,7 @@ __global__ __launch_bounds__(NTH) void k_map_fused(const uint8_t *__restrict__ f
         const uint32_t base = pass * PSTRIDE;
         const uint32_t i0 = base + (uint32_t)lane * SIG_PPT;
         uint32_t pre[16], suf[16];
-#if FK_MAPV >= 4
-        // complemented norms (FK_MAPV 4): window maxima of ~norm = ~(window minima of norm), every DPP
+        // complemented norms: window maxima of ~norm = ~(window minima of norm), every DPP
         // hop a bound_ctrl move (0 = the identity of max: no identity register, hops fused into v_max)
         uint32_t wmin[16];  // ~ window minimum
         {
@@ -579,38 +557,6 @@ __global__ __launch_bounds__(NTH) void k_map_fused(const uint8_t *__restrict__ f
                 wmin[s] = v;
             }
         }
-#else
-        {
-            uint32_t own[16];
-            fm_norm_block<MC>(s_code, (int)(i0 >> 4), own);
-            pre[0] = own[0];
-#pragma unroll
-            for (int s = 1; s < 16; ++s) pre[s] = min(pre[s - 1], own[s]);
-            suf[15] = own[15];
-#pragma unroll
-            for (int s = 14; s >= 0; --s) suf[s] = min(own[s], suf[s + 1]);
-        }
-        // successors' prefix minima: P[j][x] = pre[x] of lane + j + 1 (DPP wave_shl:1 hops)
-        uint32_t wmin[16];
-        {
-            uint32_t P[JMAX][16];
-#pragma unroll
-            for (int x = 0; x < 16; ++x) P[0][x] = dpp32<0x130, 0xf>(0xffffffffu, pre[x]);
-#pragma unroll
-            for (int j = 1; j < JMAX; ++j)
-#pragma unroll
-                for (int x = 0; x < 16; ++x) P[j][x] = dpp32<0x130, 0xf>(0xffffffffu, P[j - 1][x]);
-#pragma unroll
-            for (int s = 0; s < 16; ++s) {
-                const int e = s + w - 1;  // window end relative to i0
-                const int J = e >> 4, r = e & 15;
-                uint32_t v = min(suf[s], P[J - 1][r]);
-#pragma unroll
-                for (int j = 1; j < J; ++j) v = min(v, P[j - 1][15]);
-                wmin[s] = v;
-            }
-        }
-#endif
         // valid windows of the 16 starts: bit s <-> window at i0 + s (owned positions only)
         uint32_t vmask;
         {
@@ -644,39 +590,25 @@ __global__ __launch_bounds__(NTH) void k_map_fused(const uint8_t *__restrict__ f
         }
         nk += (uint32_t)__popc(vmask);
         // runs of equal signature, cut every 16 k-mers from the run start (as k_superkmers)
-#if FK_MAPV >= 4
         const uint32_t psig = dppz<0x138>(wmin[15]), pvmask = dppz<0x138>(vmask);  // wave_shr:1
-#else
-        const uint32_t psig = dpp32<0x138, 0xf>(0u, wmin[15]), pvmask = dpp32<0x138, 0xf>(0u, vmask);  // wave_shr:1
-#endif
-#if FK_MAPV >= 2
         // bit s = (wmin[s] != wmin[s - 1]): one compare and one add-with-carry per bit (the compiler's
         // select + OR costs 2.5)
         uint32_t neq = 0u;
 #pragma unroll
         for (int s = 15; s >= 1; --s) neq = fm_push_ne(neq, wmin[s], wmin[s - 1]);
         neq = fm_push_ne(neq, wmin[0], psig);
-#else
-        uint32_t neq = wmin[0] != psig ? 1u : 0u;
-#pragma unroll
-        for (int s = 1; s < 16; ++s) neq |= (wmin[s] != wmin[s - 1] ? 1u : 0u) << s;
-#endif
         const uint32_t pvm = (vmask << 1) | ((pvmask >> 15) & 1u);
         const uint32_t rs = vmask & (~pvm | neq);
         const int mine_rs = rs ? (int)i0 + 31 - __builtin_clz(rs) : -1;
-#if FK_MAPV >= 4
         const int prev_rs = (int)dppz<0x138>(wave_incl_max<uint32_t>((uint32_t)(mine_rs + 1))) - 1;  // exclusive
-#else
-        const int prev_rs = dpp_move<0x138, 0xf>(-1, wave_incl_max<int>(mine_rs));  // exclusive, in the pass
-#endif
         const int pc = prev_rs & 15;
         const bool cut = ((rs & ((2u << pc) - 1u)) == 0u) && ((vmask >> pc) & 1u);
         const uint32_t starts = rs | (cut ? 1u << pc : 0u);
         const uint32_t stops = (~vmask | starts) & 0xffffu;
         // wave_shl:1 (the last lane owns no windows: its successor's stops are never read)
-        const uint32_t nstops = FK_MAPV >= 4 ? dppz<0x130>(stops) : dpp32<0x130, 0xf>(0xffffu, stops);
+        const uint32_t nstops = dppz<0x130>(stops);
         const uint32_t cnt = (uint32_t)__popc(starts);
-        const uint32_t inc = FK_MAPV >= 4 ? wave_incl_sum_z(cnt) : wave_incl_sum<uint32_t>(cnt);
+        const uint32_t inc = wave_incl_sum_z(cnt);
         const uint32_t T = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
         FM_STAMP(4);  // signature pass: norms, window minima, run starts, scans
         if (probe == 3) {  // timing probe: the signature passes without the records
@@ -717,7 +649,7 @@ __global__ __launch_bounds__(NTH) void k_map_fused(const uint8_t *__restrict__ f
             for (uint32_t j = (uint32_t)lane; j < nq; j += 64) {
                 const uint32_t a = wq[j];
                 const uint32_t rel = a - base, ol = rel >> 4, sp = rel & 15u;
-                const uint32_t sig = FK_MAPV >= 4 ? ~wscr[fm_scr(ol, sp)] : wscr[fm_scr(ol, sp)];
+                const uint32_t sig = ~wscr[fm_scr(ol, sp)];  // the scratch holds complements
                 const uint32_t after = wstop[ol] & ~((2u << sp) - 1u);  // a stop lies within 16 positions
                 const int nn = __builtin_ctz(after) - (int)sp;
                 const uint32_t bin = pow2_bins ? (hash32(sig) & (fm.d - 1u)) : bin_of_signature(sig, fm);

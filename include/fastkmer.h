@@ -92,12 +92,15 @@ typedef struct fk_stats {
     /* pieces counted while later ones were still being copied in / received (sorted count) */
     uint64_t pieces_counted;   /* staged pieces of the last fk_finish (0: one count of the whole input) */
     uint64_t heavy_keys;       /* sorted count: k-mers in the buckets above the wave tier (split or block / big) */
-    uint64_t block_buckets;    /* block tier: buckets above the wave tier of at most 1024 keys (k <= 32: the mid wave
-                                  tier) / 2048 keys (k > 32: mid wave tier, LDS sort) */
-    uint64_t big_buckets;      /* above the block tier (k <= 32: split into sub-buckets, fallbacks to the block /
-                                  big-table kernels; k > 32: the streaming path) */
-    uint64_t split_buckets;    /* k <= 32: buckets above the wave tier split into wave-sized sub-buckets */
-    uint64_t sub_buckets;      /* ... into this many sub-buckets (the wave tier counted them) */
+    uint64_t block_buckets;    /* block tier: buckets above the wave tier (k <= 32: 512 keys, k > 32: 256) counted by
+                                  the mid wave tier, one wave each: up to 1024 keys (k <= 32) / 512 keys (k > 32) */
+    uint64_t big_buckets;      /* above the block tier: split into wave-sized sub-buckets (k_bucket_split64 /
+                                  k_bucket_split128) counted in order by one wave per bucket (k_sub_count64_seq /
+                                  k_sub_count128_seq); fallbacks only for a bucket the split cannot cut (a k-mer
+                                  repeated too often): the block kernel (k <= 32) / LDS sort (k > 32) up to 2048
+                                  keys, above it the big-table kernel (k <= 32) and the streaming path */
+    uint64_t split_buckets;    /* big-tier buckets the split cut into wave-sized sub-buckets (not the fallbacks) */
+    uint64_t sub_buckets;      /* ... into this many sub-buckets (one wave per bucket counted them in order) */
 } fk_stats;
 
 /* ---- host-only helpers (no GPU needed) ---------------------------------- */

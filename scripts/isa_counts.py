@@ -1,5 +1,5 @@
 """Static instruction counts of k_map_fused<512, 28, 10, 0> per phase (the s_memtime stamps of the
--DFK_PROBES build delimit the phases): python scripts/isa_counts.py [-DFK_MAPV=3 ...].  The map kernel
+-DFK_PROBES build delimit the phases): python scripts/isa_counts.py [-D... for an experiment].  The map kernel
 issues one wave64 VALU instruction per 4 cycles per SIMD (profiles/r04b_pmc_split_map.txt), so the
 VALU count of the pass body times ~29 passes per tile is its time."""
 import collections, os, subprocess, sys, tempfile
