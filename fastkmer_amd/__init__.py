@@ -128,6 +128,10 @@ def lib():
         "fk_get_bin": (ctypes.c_int, [P, I32, P, P, SZ, ctypes.POINTER(SZ)]),
         "fk_write_bins": (ctypes.c_int, [P, ctypes.c_char_p]),
         "fk_get_stats": (ctypes.c_int, [P, ctypes.POINTER(fk_stats)]),
+        "fk_kmer_bin": (ctypes.c_int, [ctypes.POINTER(fk_config), P, P]),
+        "fk_query": (ctypes.c_int, [P, P, SZ, P, P]),
+        "fk_query_device": (ctypes.c_int, [P, P, SZ, P, P]),
+        "fk_query_sequence": (ctypes.c_int, [P, ctypes.c_char_p, SZ, P, SZ, ctypes.POINTER(SZ)]),
         "fk_map_bin_kmers": (ctypes.c_int, [P, P]),
         "fk_lpt_owners": (ctypes.c_int, [P, I32, I32, P]),
         "fk_set_bin_owners": (ctypes.c_int, [P, P, P]),
@@ -236,6 +240,43 @@ def decode_keys(keys: np.ndarray, k: int) -> list[str]:
             v >>= 2
         out.append("".join(reversed(s)))
     return out
+
+
+def encode_keys(kmers: list[str], k: int) -> np.ndarray:
+    """Strings -> 2-bit keys in get_bin's layout (the inverse of decode_keys): one uint64 per k-mer
+    for k <= 32, (hi, lo) pairs (a flat array) for k > 32.  ValueError on a character other than
+    A/C/G/T or a string whose length is not k."""
+    kw = 2 if k > 32 else 1
+    out = np.zeros(len(kmers) * kw, dtype=np.uint64)
+    code = {"A": 0, "C": 1, "G": 2, "T": 3}
+    for i, s in enumerate(kmers):
+        if len(s) != k:
+            raise ValueError(f"k-mer {i} has {len(s)} characters, k = {k}")
+        v = 0
+        for ch in s:
+            if ch not in code:
+                raise ValueError(f"k-mer {i} holds {ch!r}: only A, C, G, T")
+            v = (v << 2) | code[ch]
+        if kw == 2:
+            out[2 * i], out[2 * i + 1] = v >> 64, v & 0xFFFFFFFFFFFFFFFF
+        else:
+            out[i] = v
+    return out
+
+
+def kmer_bin(key_or_str, k: int, m: int, B: int) -> int:
+    """The bin of a k-mer (a string, or a key in get_bin's layout: an int / one uint64 for k <= 32,
+    (hi, lo) for k > 32; either strand) under (k, m, B) -- fk_kmer_bin, host only."""
+    if isinstance(key_or_str, str):
+        key = encode_keys([key_or_str], k)
+    else:
+        key = np.ascontiguousarray(key_or_str, dtype=np.uint64).reshape(-1)
+    if key.size != (2 if k > 32 else 1):
+        raise ValueError(f"a key for k = {k} has {2 if k > 32 else 1} word(s)")
+    cfg = make_config(k, m, 1, B)
+    b = ctypes.c_int32(-1)
+    _check(lib().fk_kmer_bin(ctypes.byref(cfg), key.ctypes.data, ctypes.byref(b)))
+    return b.value
 
 
 @dataclasses.dataclass
@@ -457,6 +498,44 @@ class KmerCounter:
         counts = np.zeros(max(cnt, 1), dtype=np.uint32)
         _check(lib().fk_get_bin(self._h, b, keys.ctypes.data, counts.ctypes.data, max(cnt, 1), ctypes.byref(n)))
         return keys[:n.value * kw], counts[:n.value]
+
+    # -- lookups in the counted result (fk_query*)
+    def query(self, kmers, return_bins: bool = False):
+        """Counts of k-mers (a list of strings, or a uint64 array in get_bin's layout; either
+        strand): a uint32 array, 0 for an absent k-mer or a bin another rank owns.  With
+        return_bins also the int32 bin of every k-mer (-1 for a key that is no k-mer)."""
+        kw = 2 if self.k > 32 else 1
+        if isinstance(kmers, np.ndarray):
+            keys = np.ascontiguousarray(kmers, dtype=np.uint64).reshape(-1)
+        else:
+            keys = encode_keys(list(kmers), self.k)
+        if keys.size % kw:
+            raise ValueError("keys for k > 32 are (hi, lo) pairs")
+        n = keys.size // kw
+        counts = np.zeros(n, dtype=np.uint32)
+        bins = np.zeros(n, dtype=np.int32) if return_bins else None
+        _check(lib().fk_query(self._h, keys.ctypes.data, n, counts.ctypes.data,
+                              bins.ctypes.data if return_bins else None))
+        return (counts, bins) if return_bins else counts
+
+    def query_ptr(self, d_keys: int, n: int, d_counts: int, d_bins: int = 0) -> None:
+        """fk_query_device: n keys at device pointer d_keys -> uint32 counts at d_counts (and int32
+        bins at d_bins, if given), queued on the context's stream (set_stream); nothing is
+        allocated or synchronised."""
+        _check(lib().fk_query_device(self._h, ctypes.c_void_p(d_keys), n, ctypes.c_void_p(d_counts),
+                                     ctypes.c_void_p(d_bins) if d_bins else None))
+
+    def query_sequence(self, seq) -> np.ndarray:
+        """The count of every window seq[i, i + k) of a base sequence (str or bytes, no FASTA): a
+        uint32 array of len(seq) - k + 1 entries (empty when shorter), 0 for a window holding a byte
+        other than A/C/G/T."""
+        raw = seq.encode() if isinstance(seq, str) else bytes(seq)
+        n = ctypes.c_size_t(0)
+        nwin = max(len(raw) - self.k + 1, 0)
+        counts = np.zeros(nwin, dtype=np.uint32)
+        _check(lib().fk_query_sequence(self._h, raw, len(raw), counts.ctypes.data if nwin else None, nwin,
+                                       ctypes.byref(n)))
+        return counts[:n.value]
 
     def bin_dict(self, b: int) -> dict:
         keys, counts = self.get_bin(b)

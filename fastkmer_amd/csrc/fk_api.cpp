@@ -372,6 +372,8 @@ struct fk_ctx {
     uint64_t res_nbuckets = 0;
     int res_F = 0;
     DevBuf gather_keys, gather_counts;    // fk_get_bin's gather of one bin
+    // fk_query / fk_query_sequence: staging of one chunk's keys (or bases), counts and bins
+    DevBuf q_in, q_counts, q_bins;
 
     // multi-rank exchange inside the context (fk_comm_init / fk_comm_init_local): the input
     // is emitted in pieces grouped by (destination, local bin) and each piece is exchanged
@@ -579,7 +581,8 @@ FK_EXPORT int fk_create(const fk_config *cfg, fk_ctx **out) {
     c->W = cfg->k <= 32 ? 2 : 3;
     c->KW = cfg->k <= 32 ? 1 : 2;
     c->fm = make_fastmod((uint32_t)c->Bc);
-    // The product library reads nine variables: three sizes of the streamed input and six test
+    // The product library reads ten variables: three sizes of the streamed input, the lookups' staging
+    // chunk (FASTKMER_QUERY_CHUNK, read by every fk_query / fk_query_sequence call) and six test
     // hooks that steer small inputs onto paths only large or adversarial inputs reach (all
     // result-preserving).  Timing probes that alter results exist only in a library built with
     // -DFK_PROBES (python -m fastkmer_amd.build --probes).
@@ -703,6 +706,7 @@ FK_EXPORT void fk_destroy(fk_ctx *c) {
                       &c->cell_total, &c->cell_base, &c->flags, &c->flag_scan, &c->buckets, &c->keys,
                       &c->out_keys, &c->out_counts, &c->bucket_unique, &c->dense_off, &c->dense_keys,
                       &c->dense_counts, &c->bin_off, &c->misc, &c->tier_list, &c->mid, &c->sc_total, &c->gather_keys, &c->gather_counts,
+                      &c->q_in, &c->q_counts, &c->q_bins,
                       &c->sp_base, &c->sp_keys, &c->sp_subs, &c->sp_par, &c->sp_fb, &c->mid_fb};
     for (DevBuf *b : bufs) release(*b);
     for (int i = 0; i < 2; ++i) {
@@ -3240,6 +3244,113 @@ FK_EXPORT int fk_get_bin(fk_ctx *c, int32_t bin, uint64_t *keys, uint32_t *count
     if (keys)
         HIP_TRY(hipMemcpy(keys, c->dense_keys.as<uint64_t>() + b0 * c->KW, cnt * 8 * c->KW, hipMemcpyDeviceToHost));
     if (counts) HIP_TRY(hipMemcpy(counts, c->dense_counts.as<uint32_t>() + b0, cnt * 4, hipMemcpyDeviceToHost));
+    return FK_OK;
+}
+
+// ---------------------------------------------------------------------------
+// lookups in the counted result (fk_query.inc)
+// ---------------------------------------------------------------------------
+
+// keys (or windows) per staged chunk of fk_query / fk_query_sequence: FASTKMER_QUERY_CHUNK, default 16 Mi
+static uint64_t query_chunk() {
+    const char *v = getenv("FASTKMER_QUERY_CHUNK");
+    const uint64_t n = v && v[0] ? strtoull(v, nullptr, 10) : 0;
+    return n ? n : 16ull << 20;
+}
+
+// the sorted count's bucket-major arrays as the lookup kernel reads them
+static int query_tables(fk_ctx *c, QueryTables &t) {
+    if (c->cfg.use_ht)
+        return set_err(FK_E_INVALID, "lookups need the sorted count (use_ht = 0): a use_ht = 1 result is in table order");
+    if (!c->have_result || !c->gapped) return set_err(FK_E_STATE, "no result: call fk_finish or fk_reduce first");
+    t.flag_scan = c->res_fs;
+    t.buckets = c->buckets.as<Bucket>();
+    t.dense_off = c->dense_off.as<uint64_t>();
+    t.keys = c->res_keys;
+    t.counts = c->out_counts.as<uint32_t>();
+    t.owner = owner_table(c);
+    t.local = local_table(c);
+    t.nbuckets = c->res_nbuckets;
+    t.fm = c->fm;
+    t.G = c->G;
+    t.rank = (uint32_t)c->cfg.rank;
+    t.nlb = c->nlb;
+    t.k = c->cfg.k;
+    t.m = c->cfg.m;
+    t.F = c->res_F;
+    return FK_OK;
+}
+
+FK_EXPORT int fk_kmer_bin(const fk_config *cfg, const uint64_t *key, int32_t *bin) {
+    if (!cfg || !key || !bin) return set_err(FK_E_INVALID, "null argument");
+    FK_TRY(fk_config_validate(cfg));
+    const int k = cfg->k;
+    const KmerKey f = k > 32 ? KmerKey{key[0], key[1]} : KmerKey{0, key[0]};
+    if (!key_is_kmer(f, k)) return set_err(FK_E_INVALID, "the key has a bit set above bit 2k - 1 = %d", 2 * k - 1);
+    const uint32_t sig = k > 32 ? kmer_signature<true>(f, revcomp_key<true>(f, k), k, cfg->m)
+                                : kmer_signature<false>(f, revcomp_key<false>(f, k), k, cfg->m);
+    *bin = (int32_t)bin_of_signature(sig, make_fastmod((uint32_t)clamp_bins(cfg->m, cfg->B)));
+    return FK_OK;
+}
+
+FK_EXPORT int fk_query_device(fk_ctx *c, const void *d_keys, size_t n, void *d_counts, void *d_bins) {
+    if (!c) return set_err(FK_E_INVALID, "null ctx");
+    DeviceGuard dg_(c->device);
+    QueryTables t;
+    FK_TRY(query_tables(c, t));
+    if (n == 0) return FK_OK;
+    if (!d_keys || !d_counts) return set_err(FK_E_INVALID, "null argument");
+    HIP_TRY(launch_query(c->KW, t, static_cast<const uint64_t *>(d_keys), n, static_cast<uint32_t *>(d_counts),
+                         static_cast<int32_t *>(d_bins), c->stream));
+    return FK_OK;
+}
+
+FK_EXPORT int fk_query(fk_ctx *c, const uint64_t *keys, size_t n, uint32_t *counts, int32_t *bins) {
+    if (!c) return set_err(FK_E_INVALID, "null ctx");
+    DeviceGuard dg_(c->device);
+    QueryTables t;
+    FK_TRY(query_tables(c, t));
+    if (n == 0) return FK_OK;
+    if (!keys || !counts) return set_err(FK_E_INVALID, "null argument");
+    hipStream_t s = c->stream;
+    const size_t chunk = (size_t)std::min<uint64_t>(query_chunk(), n), kb = (size_t)c->KW * 8;
+    FK_TRY(ensure(c->q_in, chunk * kb));
+    FK_TRY(ensure(c->q_counts, chunk * 4));
+    if (bins) FK_TRY(ensure(c->q_bins, chunk * 4));
+    for (size_t at = 0; at < n; at += chunk) {
+        const size_t nc = std::min(chunk, n - at);
+        HIP_TRY(hipMemcpyAsync(c->q_in.p, keys + at * c->KW, nc * kb, hipMemcpyHostToDevice, s));
+        HIP_TRY(launch_query(c->KW, t, c->q_in.as<uint64_t>(), nc, c->q_counts.as<uint32_t>(),
+                             bins ? c->q_bins.as<int32_t>() : nullptr, s));
+        HIP_TRY(hipMemcpyAsync(counts + at, c->q_counts.p, nc * 4, hipMemcpyDeviceToHost, s));
+        if (bins) HIP_TRY(hipMemcpyAsync(bins + at, c->q_bins.p, nc * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));  // the staging buffers are free for the next chunk
+    }
+    return FK_OK;
+}
+
+FK_EXPORT int fk_query_sequence(fk_ctx *c, const uint8_t *seq, size_t len, uint32_t *counts, size_t cap, size_t *n) {
+    if (!c || !n) return set_err(FK_E_INVALID, "null argument");
+    DeviceGuard dg_(c->device);
+    QueryTables t;
+    FK_TRY(query_tables(c, t));
+    const size_t k = (size_t)c->cfg.k, nwin = len >= k ? len - k + 1 : 0;
+    *n = nwin;
+    if (!counts || nwin == 0) return FK_OK;
+    if (cap < nwin) return set_err(FK_E_RANGE, "the sequence has %zu windows, buffer holds %zu", nwin, cap);
+    if (!seq) return set_err(FK_E_INVALID, "null argument");
+    hipStream_t s = c->stream;
+    // windows [at, at + nc) read the bases [at, at + nc + k - 1): packed on the device (k_query_seq)
+    const size_t chunk = (size_t)std::min<uint64_t>(query_chunk(), nwin);
+    FK_TRY(ensure(c->q_in, chunk + k - 1));
+    FK_TRY(ensure(c->q_counts, chunk * 4));
+    for (size_t at = 0; at < nwin; at += chunk) {
+        const size_t nc = std::min(chunk, nwin - at);
+        HIP_TRY(hipMemcpyAsync(c->q_in.p, seq + at, nc + k - 1, hipMemcpyHostToDevice, s));
+        HIP_TRY(launch_query_seq(c->KW, t, c->q_in.as<uint8_t>(), nc, c->q_counts.as<uint32_t>(), s));
+        HIP_TRY(hipMemcpyAsync(counts + at, c->q_counts.p, nc * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
     return FK_OK;
 }
 

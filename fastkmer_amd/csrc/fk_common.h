@@ -134,6 +134,60 @@ FK_HD u128 revcomp128(u128 fwd, int k) {
     return r >> (128 - 2 * k);
 }
 
+// ---- lookups: a k-mer key as (hi, lo) words (fk_get_bin's layout; hi = 0 for k <= 32) ----
+
+struct KmerKey {
+    uint64_t hi, lo;
+};
+
+FK_HD bool key_less(const KmerKey &a, const KmerKey &b) { return a.hi < b.hi || (a.hi == b.hi && a.lo < b.lo); }
+
+// no bit set above bit 2k - 1
+FK_HD bool key_is_kmer(const KmerKey &x, int k) {
+    if (k >= 64) return true;
+    if (k >= 32) return (k == 32 ? x.hi : (x.hi >> (2 * k - 64))) == 0;
+    return x.hi == 0 && (x.lo >> (2 * k)) == 0;
+}
+
+// TWO = k > 32 (revcomp128), else revcomp64 of the low word
+template <bool TWO>
+FK_HD KmerKey revcomp_key(const KmerKey &f, int k) {
+    if (!TWO) return KmerKey{0, revcomp64(f.lo, k)};
+    const u128 r = revcomp128(((u128)f.hi << 64) | f.lo, k);
+    return KmerKey{(uint64_t)(r >> 64), (uint64_t)r};
+}
+
+// The signature of a k-mer: the minimum of norm_mmer over its k - m + 1 m-mers (4^m when every
+// m-mer is forbidden on both strands) -- the signature of the super-k-mer that holds the k-mer
+// (get_super_kmers_read keeps the true minimum over the window; the norm is strand-symmetric).
+// The reverse complement's m-mers are the reverse complements of the forward m-mers, so the
+// minimum over both keys' m-mers of (allowed ? v : 4^m) is that minimum: two shifted scans, no
+// revcomp_mmer.  f: the key, r = revcomp_key(f, k) (either order).  TWO = false: hi words are 0.
+template <bool TWO>
+FK_HD uint32_t kmer_signature(KmerKey f, KmerKey r, int k, int m) {
+    const uint32_t def = 1u << (2 * m), mask = def - 1u;
+    uint32_t sig = def;
+    for (int j = k - m; j >= 0; --j) {
+        const uint32_t a = (uint32_t)f.lo & mask, b = (uint32_t)r.lo & mask;
+        const uint32_t va = is_allowed(a, m) ? a : def, vb = is_allowed(b, m) ? b : def;
+        const uint32_t v = va < vb ? va : vb;
+        sig = v < sig ? v : sig;
+        f.lo >>= 2, r.lo >>= 2;
+        if (TWO) {
+            f.lo |= f.hi << 62, r.lo |= r.hi << 62;
+            f.hi >>= 2, r.hi >>= 2;
+        }
+    }
+    return sig;
+}
+
+// The top F bits (1 <= F <= min(2k, 32)) of a 2k-bit key: its cell in the sorted count's result.
+FK_HD uint32_t key_cell(const KmerKey &x, int k, int F) {
+    const int sh = 2 * k - F;
+    const uint64_t c = sh >= 64 ? (x.hi >> (sh - 64)) : sh == 0 ? x.lo : ((x.hi << (64 - sh)) | (x.lo >> sh));
+    return (uint32_t)c;
+}
+
 // ---- deterministic synthetic reads ----------------
 
 FK_HD uint64_t splitmix64(uint64_t x) {

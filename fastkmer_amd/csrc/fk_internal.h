@@ -313,6 +313,29 @@ hipError_t launch_bucket_compact(int KW, const uint64_t *out_keys, const uint32_
 hipError_t launch_bin_offsets(const uint64_t *flag_scan, const uint64_t *dense_off, uint32_t nlbins, int F,
                               uint64_t nbuckets, uint64_t *bin_off, hipStream_t s);
 
+// ---- lookups in the sorted count's bucket-major result (fk_query.inc)
+struct QueryTables {
+    const uint64_t *flag_scan;  // (nlb << F) + 1 entries: the buckets that start before cell g, then their total
+    const Bucket *buckets;
+    const uint64_t *dense_off;  // nbuckets + 1: exclusive scan of the buckets' distinct keys
+    const uint64_t *keys;       // bucket q's distinct keys ascending at keys + KW * buckets[q].begin
+    const uint32_t *counts;     // ... and their counts at counts + buckets[q].begin
+    const uint32_t *owner, *local;  // size-aware placement: bin -> rank, bin -> local bin (null: bin % G, bin / G)
+    uint64_t nbuckets;
+    FastMod fm;
+    uint32_t G, rank, nlb;
+    int k, m, F;
+};
+// counts[i] = occurrences of the canonical k-mer of keys[i] (one word, or (hi, lo) for KW = 2; either
+// strand) when this rank owns its bin, else 0; bins[i] (bins may be null) = its bin, whoever owns it;
+// a key with a bit above 2k - 1: (0, -1)
+hipError_t launch_query(int KW, const QueryTables &t, const uint64_t *keys, uint64_t n, uint32_t *counts,
+                        int32_t *bins, hipStream_t s);
+// counts[i] for the window seq[i, i + k), i < nwin (seq holds nwin + k - 1 bytes); 0 for a window with
+// a byte other than A/C/G/T
+hipError_t launch_query_seq(int KW, const QueryTables &t, const uint8_t *seq, uint64_t nwin, uint32_t *counts,
+                            hipStream_t s);
+
 // ---- test hook: the 128-bit wave tier's fingerprints cut to `bits` low bits (0: whole), current device
 hipError_t set_fingerprint_bits(int bits);
 

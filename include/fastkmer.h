@@ -294,6 +294,38 @@ int fk_get_bin(fk_ctx *ctx, int32_t bin, uint64_t *keys, uint32_t *counts, size_
 int fk_write_bins(fk_ctx *ctx, const char *out_dir);
 int fk_get_stats(fk_ctx *ctx, fk_stats *out);
 
+/* ---- lookups in the counted result (no reference counterpart) ----
+ * How often does a k-mer occur?  Keys use fk_get_bin's layout (one word for
+ * k <= 32, (hi, lo) for k > 32, 2 bits per base, most significant base first)
+ * and may be on either strand: the library canonicalises them.
+ *   counts[i]: occurrences of the canonical k-mer in the job's input when this
+ *     rank owns the k-mer's bin, else 0; 0 for a k-mer the input does not hold.
+ *   bins (may be NULL): bins[i] = the k-mer's bin in [0, b), whoever owns it.
+ * A key with a bit set above bit 2k - 1 is no k-mer: count 0, bin -1.
+ * The calls are not collective and move nothing between ranks: the sum of the
+ * ranks' counts is the job's answer, and bins with fk_bin_owners lets a caller
+ * route its queries.  They need a result (FK_E_STATE before fk_finish /
+ * fk_reduce and after a new job's first fk_ingest) of the sorted count
+ * (use_ht == 1: FK_E_INVALID, its results are in table order), read it only,
+ * and answer the same before and after fk_get_bin / fk_write_bins.
+ *   fk_query: host pointers; staged through the context's device buffers in
+ *     chunks of FASTKMER_QUERY_CHUNK keys (default 16 Mi); returns once counts
+ *     and bins are filled.
+ *   fk_query_device: pointers on the context's device (d_counts uint32[n],
+ *     d_bins int32[n] or NULL); only queues the lookup on the context's stream
+ *     (the caller's after fk_set_stream): no allocation, no synchronisation.
+ *   fk_query_sequence: seq holds bases only (no FASTA); *n = len - k + 1
+ *     windows (0 when len < k), counts[i] = the count of seq[i, i + k), 0 for a
+ *     window with a byte other than A/C/G/T (N, lowercase, newline).
+ *     FK_E_RANGE when cap < *n; counts == NULL: only *n. */
+/* Host only: the bin of a k-mer under cfg (k, m, B): hash_to_bucket(the minimum
+ * norm over its k - m + 1 m-mers, b).  FK_E_INVALID for a configuration
+ * fk_config_validate refuses or a key that is no k-mer. */
+int fk_kmer_bin(const fk_config *cfg, const uint64_t *key, int32_t *bin);
+int fk_query(fk_ctx *ctx, const uint64_t *keys, size_t n, uint32_t *counts, int32_t *bins);
+int fk_query_device(fk_ctx *ctx, const void *d_keys, size_t n, void *d_counts, void *d_bins);
+int fk_query_sequence(fk_ctx *ctx, const uint8_t *seq, size_t len, uint32_t *counts, size_t cap, size_t *n);
+
 /* ---- test hook (no reference counterpart) ----
  * One bucket through the wave-tier count kernel on `device`: the n keys
  * (k <= 32: one word each, n <= 512; 33 <= k <= 63: (hi, lo) pairs, n <= 256)
