@@ -63,6 +63,16 @@ class fk_stats(ctypes.Structure):
                                        ("sub_buckets", ctypes.c_uint64)]
 
 COMM_ID_BYTES = 128
+MAX_COUNT = 0xFFFFFFFF  # max_count of the count-range calls: no upper bound
+
+
+def _count_range(min_count, max_count):
+    """(lo, hi) of a count range for the C calls, or None for the default (every k-mer)."""
+    hi = MAX_COUNT if max_count is None else int(max_count)
+    lo = int(min_count)
+    if not (0 <= lo <= MAX_COUNT and 0 <= hi <= MAX_COUNT):
+        raise ValueError("min_count / max_count are 32-bit counts")
+    return None if (lo, hi) == (1, MAX_COUNT) else (lo, hi)
 
 
 _lib = None
@@ -132,6 +142,12 @@ def lib():
         "fk_query": (ctypes.c_int, [P, P, SZ, P, P]),
         "fk_query_device": (ctypes.c_int, [P, P, SZ, P, P]),
         "fk_query_sequence": (ctypes.c_int, [P, ctypes.c_char_p, SZ, P, SZ, ctypes.POINTER(SZ)]),
+        "fk_spectrum": (ctypes.c_int, [P, P, SZ, P]),
+        "fk_spectrum_device": (ctypes.c_int, [P, P, SZ, P]),
+        "fk_bin_sizes_range": (ctypes.c_int, [P, ctypes.c_uint32, ctypes.c_uint32, P]),
+        "fk_get_bin_range": (ctypes.c_int, [P, I32, ctypes.c_uint32, ctypes.c_uint32, P, P, SZ,
+                                            ctypes.POINTER(SZ)]),
+        "fk_write_bins_range": (ctypes.c_int, [P, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32]),
         "fk_map_bin_kmers": (ctypes.c_int, [P, P]),
         "fk_lpt_owners": (ctypes.c_int, [P, I32, I32, P]),
         "fk_set_bin_owners": (ctypes.c_int, [P, P, P]),
@@ -483,21 +499,51 @@ class KmerCounter:
         return lib().fk_comm_transport(self._h).decode()
 
     # -- results
-    def bin_sizes(self) -> np.ndarray:
+    # min_count / max_count (results): only the k-mers with min_count <= count <= max_count, both ends
+    # inclusive (max_count None: no upper bound), filtered on the device (fk_*_range); the defaults
+    # are the unfiltered calls.
+    def bin_sizes(self, min_count: int = 1, max_count: int | None = None) -> np.ndarray:
         out = np.zeros(self.num_bins, dtype=np.uint64)
-        _check(lib().fk_bin_sizes(self._h, out.ctypes.data))
+        rg = _count_range(min_count, max_count)
+        if rg is None:
+            _check(lib().fk_bin_sizes(self._h, out.ctypes.data))
+        else:
+            _check(lib().fk_bin_sizes_range(self._h, rg[0], rg[1], out.ctypes.data))
         return out
 
-    def get_bin(self, b: int):
+    def get_bin(self, b: int, min_count: int = 1, max_count: int | None = None):
         n = ctypes.c_size_t(0)
+        rg = _count_range(min_count, max_count)
         if self._sizes is None:
             self._sizes = self.bin_sizes()
-        cnt = int(self._sizes[b])
+        cnt = int(self._sizes[b])  # the unfiltered size bounds a filtered bin
         kw = 2 if self.k > 32 else 1
         keys = np.zeros(max(cnt, 1) * kw, dtype=np.uint64)
         counts = np.zeros(max(cnt, 1), dtype=np.uint32)
-        _check(lib().fk_get_bin(self._h, b, keys.ctypes.data, counts.ctypes.data, max(cnt, 1), ctypes.byref(n)))
+        if rg is None:
+            _check(lib().fk_get_bin(self._h, b, keys.ctypes.data, counts.ctypes.data, max(cnt, 1), ctypes.byref(n)))
+        else:
+            _check(lib().fk_get_bin_range(self._h, b, rg[0], rg[1], keys.ctypes.data, counts.ctypes.data,
+                                          max(cnt, 1), ctypes.byref(n)))
         return keys[:n.value * kw], counts[:n.value]
+
+    # -- abundance spectrum (fk_spectrum*)
+    def spectrum(self, n: int = 256, return_tail: bool = False):
+        """The abundance spectrum of this rank's k-mers: a uint64 array of n >= 2 entries, hist[c] =
+        distinct k-mers with count c for 1 <= c <= n - 2, hist[n - 1] = those with count >= n - 1
+        (hist[0] = 0).  With return_tail also the sum of the counts of the k-mers in the last entry.
+        The job's spectrum is the sum over the ranks (comm_allreduce)."""
+        hist = np.zeros(max(int(n), 1), dtype=np.uint64)
+        tail = ctypes.c_uint64(0)
+        _check(lib().fk_spectrum(self._h, hist.ctypes.data, int(n), ctypes.byref(tail)))
+        return (hist, int(tail.value)) if return_tail else hist
+
+    def spectrum_ptr(self, d_hist: int, n: int, d_tail: int = 0) -> None:
+        """fk_spectrum_device: the spectrum into uint64[n] at device pointer d_hist (and the tail's
+        k-mer sum into uint64[1] at d_tail, if given), overwritten, queued on the context's stream
+        (set_stream); nothing is allocated or synchronised."""
+        _check(lib().fk_spectrum_device(self._h, ctypes.c_void_p(d_hist), int(n),
+                                        ctypes.c_void_p(d_tail) if d_tail else None))
 
     # -- lookups in the counted result (fk_query*)
     def query(self, kmers, return_bins: bool = False):
@@ -537,21 +583,27 @@ class KmerCounter:
                                        ctypes.byref(n)))
         return counts[:n.value]
 
-    def bin_dict(self, b: int) -> dict:
-        keys, counts = self.get_bin(b)
+    def bin_dict(self, b: int, min_count: int = 1, max_count: int | None = None) -> dict:
+        keys, counts = self.get_bin(b, min_count, max_count)
         return dict(zip(decode_keys(keys, self.k), (int(c) for c in counts)))
 
     def all_dict(self) -> dict:
         sizes = self.bin_sizes()
         return {b: self.bin_dict(b) for b in np.nonzero(sizes)[0].tolist()}
 
-    def bin_text(self, b: int) -> str:
-        keys, counts = self.get_bin(b)
+    def bin_text(self, b: int, min_count: int = 1, max_count: int | None = None) -> str:
+        keys, counts = self.get_bin(b, min_count, max_count)
         lines = [f"{s}\t{int(c)}\n" for s, c in zip(decode_keys(keys, self.k), counts)]
+        if not lines and _count_range(min_count, max_count) is not None:
+            return ""  # a bin with no kept line has no file, so no trailer either
         return "".join(lines) + ("" if self.use_ht else "EOF")
 
-    def write_bins(self, out_dir: str) -> None:
-        _check(lib().fk_write_bins(self._h, out_dir.encode()))
+    def write_bins(self, out_dir: str, min_count: int = 1, max_count: int | None = None) -> None:
+        rg = _count_range(min_count, max_count)
+        if rg is None:
+            _check(lib().fk_write_bins(self._h, out_dir.encode()))
+        else:
+            _check(lib().fk_write_bins_range(self._h, out_dir.encode(), rg[0], rg[1]))
 
     # -- bin-signature diagnostics (executeFindBinSignaturesJob, SBKC:956-986)
     def signature_counts(self, out=None):

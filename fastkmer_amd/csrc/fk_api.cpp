@@ -280,6 +280,7 @@ struct fk_ctx {
     int mid_parts = -1;        // FASTKMER_DEBUG_MID_PARTS: the 64-bit mid tier's key ranges always (1), the whole
                                // buckets on the 512-key table always (2), the 1024-key kernel only (0), by size (-1)
     bool split_retry = false;  // FASTKMER_DEBUG_SPLIT_RETRY: every split bucket cut a second time
+    bool spectrum_wide = false;  // FASTKMER_DEBUG_SPECTRUM_WIDE: the spectrum kernel of results of >= 2^32 k-mers
     int x2_l1 = 0;             // FASTKMER_X2_L1: level-1 workgroup size (512, 1024; 0 = by fan-out)
     int fused = 1;             // FASTKMER_FUSED=0: two-kernel map (parse, then signature) for every input
 #ifdef FK_PROBES
@@ -374,6 +375,9 @@ struct fk_ctx {
     DevBuf gather_keys, gather_counts;    // fk_get_bin's gather of one bin
     // fk_query / fk_query_sequence: staging of one chunk's keys (or bases), counts and bins
     DevBuf q_in, q_counts, q_bins;
+    // fk_spectrum: the histogram and its tail sum; fk_get_bin_range: kept k-mers per bucket of one bin
+    // and their scan (the filtered bin itself goes through gather_keys / gather_counts)
+    DevBuf sp_hist, rg_kept, rg_off;
 
     // multi-rank exchange inside the context (fk_comm_init / fk_comm_init_local): the input
     // is emitted in pieces grouped by (destination, local bin) and each piece is exchanged
@@ -581,8 +585,8 @@ FK_EXPORT int fk_create(const fk_config *cfg, fk_ctx **out) {
     c->W = cfg->k <= 32 ? 2 : 3;
     c->KW = cfg->k <= 32 ? 1 : 2;
     c->fm = make_fastmod((uint32_t)c->Bc);
-    // The product library reads ten variables: three sizes of the streamed input, the lookups' staging
-    // chunk (FASTKMER_QUERY_CHUNK, read by every fk_query / fk_query_sequence call) and six test
+    // The product library reads eleven variables: three sizes of the streamed input, the lookups' staging
+    // chunk (FASTKMER_QUERY_CHUNK, read by every fk_query / fk_query_sequence call) and seven test
     // hooks that steer small inputs onto paths only large or adversarial inputs reach (all
     // result-preserving).  Timing probes that alter results exist only in a library built with
     // -DFK_PROBES (python -m fastkmer_amd.build --probes).
@@ -611,6 +615,7 @@ FK_EXPORT int fk_create(const fk_config *cfg, fk_ctx **out) {
     if (const char *v = env("FASTKMER_DEBUG_CELL_TARGET")) c->cell_target = (uint32_t)atoi(v);
     if (const char *v = env("FASTKMER_DEBUG_MID_PARTS")) c->mid_parts = atoi(v);  // test hook: 1 / 2 / 0
     if (const char *v = env("FASTKMER_DEBUG_SPLIT_RETRY")) c->split_retry = v[0] == '1';  // test hook
+    if (const char *v = env("FASTKMER_DEBUG_SPECTRUM_WIDE")) c->spectrum_wide = v[0] == '1';  // test hook
     if (const char *v = env("FASTKMER_X2_L1")) c->x2_l1 = atoi(v);
     if (const char *v = env("FASTKMER_FUSED")) c->fused = atoi(v);
 #ifdef FK_PROBES
@@ -706,7 +711,7 @@ FK_EXPORT void fk_destroy(fk_ctx *c) {
                       &c->cell_total, &c->cell_base, &c->flags, &c->flag_scan, &c->buckets, &c->keys,
                       &c->out_keys, &c->out_counts, &c->bucket_unique, &c->dense_off, &c->dense_keys,
                       &c->dense_counts, &c->bin_off, &c->misc, &c->tier_list, &c->mid, &c->sc_total, &c->gather_keys, &c->gather_counts,
-                      &c->q_in, &c->q_counts, &c->q_bins,
+                      &c->q_in, &c->q_counts, &c->q_bins, &c->sp_hist, &c->rg_kept, &c->rg_off,
                       &c->sp_base, &c->sp_keys, &c->sp_subs, &c->sp_par, &c->sp_fb, &c->mid_fb};
     for (DevBuf *b : bufs) release(*b);
     for (int i = 0; i < 2; ++i) {
@@ -3478,19 +3483,15 @@ static int mkdir_p(const std::string &path) {
     return 0;
 }
 
-// Bin files (writers SBKC:550-606 / 715-734): the text is formatted on the
-// device (fk_format.inc), copied to the host once and written one file per bin.
-FK_EXPORT int fk_write_bins(fk_ctx *c, const char *out_dir) {
-    if (!c || !out_dir) return set_err(FK_E_INVALID, "null argument");
-    DeviceGuard dg_(c->device);
-    if (!c->have_result) return set_err(FK_E_STATE, "no result: call fk_finish or fk_reduce first");
-    if (mkdir_p(out_dir) != 0) return set_err(FK_E_IO, "cannot create %s: %s", out_dir, strerror(errno));
+// Bin files (writers SBKC:550-606 / 715-734) of D dense lines (device keys / counts in bin order,
+// bin_off / h_bin_off their nlb + 1 offsets per local bin on the device / host): the text is
+// formatted on the device (fk_format.inc), copied to the host once and written one file per bin.
+static int write_bin_text(fk_ctx *c, const char *out_dir, const uint64_t *keys, const uint32_t *counts, uint64_t D,
+                          const uint64_t *bin_off, const std::vector<uint64_t> &h_bin_off) {
     hipStream_t s = c->stream;
-    const uint64_t D = c->distinct;
     const uint32_t nlb = c->nlb;
     const int eof = c->cfg.use_ht == 0;
     if (D == 0) return FK_OK;  // no k-mers: no bin files
-    FK_TRY(materialize_dense(c));
     DevBuf len, off, bbytes, text;
     struct Free {
         DevBuf *b[4];
@@ -3501,18 +3502,15 @@ FK_EXPORT int fk_write_bins(fk_ctx *c, const char *out_dir) {
     FK_TRY(ensure(len, D * 4));
     FK_TRY(ensure(off, (D + 1) * 8));
     FK_TRY(ensure(bbytes, ((uint64_t)nlb + 1) * 8));
-    HIP_TRY(launch_format_lens(c->dense_counts.as<uint32_t>(), D, c->cfg.k, c->bin_off.as<uint64_t>(), nlb, eof,
-                               len.as<uint32_t>(), s));
+    HIP_TRY(launch_format_lens(counts, D, c->cfg.k, bin_off, nlb, eof, len.as<uint32_t>(), s));
     HIP_TRY(scan_excl_sum_u32_to_u64(len.as<uint32_t>(), off.as<uint64_t>(), D, off.as<uint64_t>() + D, c->ws, s));
-    HIP_TRY(launch_gather_u64(off.as<uint64_t>(), c->bin_off.as<uint64_t>(), (uint64_t)nlb + 1,
-                              bbytes.as<uint64_t>(), s));
+    HIP_TRY(launch_gather_u64(off.as<uint64_t>(), bin_off, (uint64_t)nlb + 1, bbytes.as<uint64_t>(), s));
     std::vector<uint64_t> bb(nlb + 1, 0);
     HIP_TRY(hipMemcpyAsync(bb.data(), bbytes.p, ((uint64_t)nlb + 1) * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     const uint64_t T = bb[nlb];
     FK_TRY(ensure(text, T + 16));
-    HIP_TRY(launch_format_lines(c->KW, c->dense_keys.as<uint64_t>(), c->dense_counts.as<uint32_t>(), D, c->cfg.k,
-                                off.as<uint64_t>(), text.as<uint8_t>(), s));
+    HIP_TRY(launch_format_lines(c->KW, keys, counts, D, c->cfg.k, off.as<uint64_t>(), text.as<uint8_t>(), s));
     uint8_t *host = nullptr;
     if (T) {
         HIP_TRY(hipHostMalloc((void **)&host, T, hipHostMallocDefault));
@@ -3530,7 +3528,7 @@ FK_EXPORT int fk_write_bins(fk_ctx *c, const char *out_dir) {
     for (unsigned t = 0; t < nth; ++t) {
         th.emplace_back([&, t]() {
             for (uint32_t lb = t; lb < nlb; lb += nth) {
-                if (c->h_bin_off[lb + 1] == c->h_bin_off[lb]) continue;  // empty bins have no file
+                if (h_bin_off[lb + 1] == h_bin_off[lb]) continue;  // empty bins have no file
                 const std::string path = dir + "/bin" + std::to_string(global_bin(c, lb));
                 FILE *f = fopen(path.c_str(), "wb");
                 const size_t nb = (size_t)(bb[lb + 1] - bb[lb]);
@@ -3544,6 +3542,180 @@ FK_EXPORT int fk_write_bins(fk_ctx *c, const char *out_dir) {
     for (int e : errs)
         if (e) return set_err(FK_E_IO, "writing bin files under %s failed", out_dir);
     return FK_OK;
+}
+
+FK_EXPORT int fk_write_bins(fk_ctx *c, const char *out_dir) {
+    if (!c || !out_dir) return set_err(FK_E_INVALID, "null argument");
+    DeviceGuard dg_(c->device);
+    if (!c->have_result) return set_err(FK_E_STATE, "no result: call fk_finish or fk_reduce first");
+    if (mkdir_p(out_dir) != 0) return set_err(FK_E_IO, "cannot create %s: %s", out_dir, strerror(errno));
+    if (c->distinct == 0) return FK_OK;  // no k-mers: no bin files
+    FK_TRY(materialize_dense(c));
+    return write_bin_text(c, out_dir, c->dense_keys.as<uint64_t>(), c->dense_counts.as<uint32_t>(), c->distinct,
+                          c->bin_off.as<uint64_t>(), c->h_bin_off);
+}
+
+// ---------------------------------------------------------------------------
+// abundance spectrum and count-range views of the counted result (fk_spectrum.inc); either count mode
+// ---------------------------------------------------------------------------
+
+static int result_ready(const fk_ctx *c) {
+    if (!c->have_result) return set_err(FK_E_STATE, "no result: call fk_finish or fk_reduce first");
+    if (c->distinct && !c->gapped) return set_err(FK_E_STATE, "the result is not bucket-major");
+    return FK_OK;
+}
+
+static int check_count_range(uint32_t lo, uint32_t hi) {
+    if (lo == 0) return set_err(FK_E_INVALID, "min_count must be >= 1 (no k-mer of the result has count 0)");
+    if (lo > hi) return set_err(FK_E_INVALID, "min_count %u > max_count %u", lo, hi);
+    return FK_OK;
+}
+
+static int spectrum_launch(fk_ctx *c, uint64_t *d_hist, size_t n, uint64_t *d_tail) {
+    // an empty job has no buckets: the launcher only clears the outputs
+    HIP_TRY(launch_spectrum(c->out_counts.as<uint32_t>(), c->buckets.as<Bucket>(), c->dense_off.as<uint64_t>(),
+                            c->distinct ? c->res_nbuckets : 0, c->spectrum_wide ? ~0ull : c->distinct, d_hist, n, d_tail,
+                            c->stream));
+    return FK_OK;
+}
+
+FK_EXPORT int fk_spectrum_device(fk_ctx *c, void *d_hist, size_t n, void *d_tail_kmers) {
+    if (!c) return set_err(FK_E_INVALID, "null ctx");
+    DeviceGuard dg_(c->device);
+    FK_TRY(result_ready(c));
+    if (n < 2) return set_err(FK_E_INVALID, "a spectrum has n >= 2 entries");
+    if (!d_hist) return set_err(FK_E_INVALID, "null argument");
+    return spectrum_launch(c, static_cast<uint64_t *>(d_hist), n, static_cast<uint64_t *>(d_tail_kmers));
+}
+
+FK_EXPORT int fk_spectrum(fk_ctx *c, uint64_t *hist, size_t n, uint64_t *tail_kmers) {
+    if (!c) return set_err(FK_E_INVALID, "null ctx");
+    DeviceGuard dg_(c->device);
+    FK_TRY(result_ready(c));
+    if (n < 2) return set_err(FK_E_INVALID, "a spectrum has n >= 2 entries");
+    if (!hist) return set_err(FK_E_INVALID, "null argument");
+    FK_TRY(ensure(c->sp_hist, ((uint64_t)n + 1) * 8));
+    uint64_t *d = c->sp_hist.as<uint64_t>();
+    FK_TRY(spectrum_launch(c, d, n, d + n));
+    HIP_TRY(hipMemcpyAsync(hist, d, (uint64_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+    if (tail_kmers) HIP_TRY(hipMemcpyAsync(tail_kmers, d + n, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return FK_OK;
+}
+
+// The whole result filtered to [lo, hi]: kept k-mers per bucket -> their scan -> offsets per local bin
+// (d_off on the device, h_off their copy on the host).  kept / off / d_off: the caller's temporaries.
+static int range_offsets(fk_ctx *c, uint32_t lo, uint32_t hi, DevBuf &kept, DevBuf &off, DevBuf &d_off,
+                         std::vector<uint64_t> &h_off) {
+    hipStream_t s = c->stream;
+    const uint64_t nb = c->res_nbuckets;
+    const uint32_t nlb = c->nlb;
+    FK_TRY(ensure(kept, nb * 8));
+    FK_TRY(ensure(off, (nb + 1) * 8));
+    FK_TRY(ensure(d_off, ((uint64_t)nlb + 1) * 8));
+    HIP_TRY(launch_range_count(c->out_counts.as<uint32_t>(), c->buckets.as<Bucket>(), c->dense_off.as<uint64_t>(), nb,
+                               lo, hi, kept.as<uint64_t>(), s));
+    HIP_TRY(scan_excl_sum_u64(kept.as<uint64_t>(), off.as<uint64_t>(), nb, off.as<uint64_t>() + nb, c->ws, s));
+    HIP_TRY(launch_bin_offsets(c->res_fs, off.as<uint64_t>(), nlb, c->res_F, nb, d_off.as<uint64_t>(), s));
+    h_off.assign((size_t)nlb + 1, 0);
+    HIP_TRY(hipMemcpyAsync(h_off.data(), d_off.p, ((uint64_t)nlb + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return FK_OK;
+}
+
+struct FreeBufs {
+    std::vector<DevBuf *> b;
+    ~FreeBufs() {
+        for (DevBuf *x : b) release(*x);
+    }
+};
+
+FK_EXPORT int fk_bin_sizes_range(fk_ctx *c, uint32_t min_count, uint32_t max_count, uint64_t *out) {
+    if (!c || !out) return set_err(FK_E_INVALID, "null argument");
+    DeviceGuard dg_(c->device);
+    FK_TRY(result_ready(c));
+    FK_TRY(check_count_range(min_count, max_count));
+    for (int32_t b = 0; b < c->Bc; ++b) out[b] = 0;
+    if (c->distinct == 0) return FK_OK;
+    DevBuf kept, off, d_off;
+    FreeBufs guard{{&kept, &off, &d_off}};
+    std::vector<uint64_t> h_off;
+    FK_TRY(range_offsets(c, min_count, max_count, kept, off, d_off, h_off));
+    for (int32_t b = 0; b < c->Bc; ++b)
+        if (owns(c, b)) {
+            const uint32_t lb = local_bin(c, b);
+            out[b] = h_off[lb + 1] - h_off[lb];
+        }
+    return FK_OK;
+}
+
+// One bin filtered: the two range kernels over the bin's buckets [q0, q1) only (gather_bin's).
+FK_EXPORT int fk_get_bin_range(fk_ctx *c, int32_t bin, uint32_t min_count, uint32_t max_count, uint64_t *keys,
+                               uint32_t *counts, size_t cap, size_t *n) {
+    if (!c || !n) return set_err(FK_E_INVALID, "null argument");
+    DeviceGuard dg_(c->device);
+    FK_TRY(result_ready(c));
+    FK_TRY(check_count_range(min_count, max_count));
+    if (bin < 0 || bin >= c->Bc) return set_err(FK_E_RANGE, "bin %d out of [0, %d)", bin, c->Bc);
+    *n = 0;
+    if (!owns(c, bin) || c->distinct == 0) return FK_OK;
+    const uint32_t lb = local_bin(c, bin);
+    if (c->h_bin_off[lb + 1] == c->h_bin_off[lb]) return FK_OK;
+    hipStream_t s = c->stream;
+    uint64_t q[2] = {0, c->res_nbuckets};
+    const uint64_t *fs = c->res_fs;
+    HIP_TRY(hipMemcpyAsync(&q[0], fs + ((uint64_t)lb << c->res_F), 8, hipMemcpyDeviceToHost, s));
+    if (lb + 1 < c->nlb) HIP_TRY(hipMemcpyAsync(&q[1], fs + ((uint64_t)(lb + 1) << c->res_F), 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (q[1] <= q[0] || q[1] > c->res_nbuckets) return FK_OK;
+    const uint64_t nq = q[1] - q[0];
+    FK_TRY(ensure(c->rg_kept, nq * 8));
+    FK_TRY(ensure(c->rg_off, (nq + 1) * 8));
+    const Bucket *bk = c->buckets.as<Bucket>() + q[0];
+    const uint64_t *doff = c->dense_off.as<uint64_t>() + q[0];
+    uint64_t *koff = c->rg_off.as<uint64_t>();
+    HIP_TRY(launch_range_count(c->out_counts.as<uint32_t>(), bk, doff, nq, min_count, max_count,
+                               c->rg_kept.as<uint64_t>(), s));
+    HIP_TRY(scan_excl_sum_u64(c->rg_kept.as<uint64_t>(), koff, nq, koff + nq, c->ws, s));
+    uint64_t cnt = 0;
+    HIP_TRY(hipMemcpyAsync(&cnt, koff + nq, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *n = (size_t)cnt;
+    if (cnt == 0) return FK_OK;
+    if (cap < cnt)
+        return set_err(FK_E_RANGE, "bin %d has %llu k-mers with counts in [%u, %u], buffer holds %zu", bin,
+                       (unsigned long long)cnt, min_count, max_count, cap);
+    if (!keys && !counts) return FK_OK;
+    FK_TRY(ensure(c->gather_keys, cnt * 8 * c->KW));
+    FK_TRY(ensure(c->gather_counts, cnt * 4));
+    HIP_TRY(launch_range_compact(c->KW, c->res_keys, c->out_counts.as<uint32_t>(), bk, doff, koff, nq, min_count,
+                                 max_count, c->gather_keys.as<uint64_t>(), c->gather_counts.as<uint32_t>(), s));
+    if (keys) HIP_TRY(hipMemcpyAsync(keys, c->gather_keys.p, cnt * 8 * c->KW, hipMemcpyDeviceToHost, s));
+    if (counts) HIP_TRY(hipMemcpyAsync(counts, c->gather_counts.p, cnt * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return FK_OK;
+}
+
+FK_EXPORT int fk_write_bins_range(fk_ctx *c, const char *out_dir, uint32_t min_count, uint32_t max_count) {
+    if (!c || !out_dir) return set_err(FK_E_INVALID, "null argument");
+    DeviceGuard dg_(c->device);
+    FK_TRY(result_ready(c));
+    FK_TRY(check_count_range(min_count, max_count));
+    if (mkdir_p(out_dir) != 0) return set_err(FK_E_IO, "cannot create %s: %s", out_dir, strerror(errno));
+    if (c->distinct == 0) return FK_OK;  // no k-mers: no bin files
+    DevBuf kept, off, d_off, fkeys, fcounts;
+    FreeBufs guard{{&kept, &off, &d_off, &fkeys, &fcounts}};
+    std::vector<uint64_t> h_off;
+    FK_TRY(range_offsets(c, min_count, max_count, kept, off, d_off, h_off));
+    const uint64_t D = h_off[c->nlb];
+    if (D == 0) return FK_OK;  // nothing kept: no bin files
+    FK_TRY(ensure(fkeys, D * 8 * c->KW));
+    FK_TRY(ensure(fcounts, D * 4));
+    HIP_TRY(launch_range_compact(c->KW, c->res_keys, c->out_counts.as<uint32_t>(), c->buckets.as<Bucket>(),
+                                 c->dense_off.as<uint64_t>(), off.as<uint64_t>(), c->res_nbuckets, min_count,
+                                 max_count, fkeys.as<uint64_t>(), fcounts.as<uint32_t>(), c->stream));
+    // the writer ends with the stream drained (its text copy), before the temporaries are released
+    return write_bin_text(c, out_dir, fkeys.as<uint64_t>(), fcounts.as<uint32_t>(), D, d_off.as<uint64_t>(), h_off);
 }
 
 // ---------------------------------------------------------------------------

@@ -9,6 +9,14 @@
 // TestConfiguration.outputDir (test/package.scala:33).  enableKryo selects a
 // JVM serializer and useCustomPartitioner a Spark placement: neither changes
 // the counts, both are accepted and reported.
+//
+// Beyond the reference (read here only, the positional contract is untouched; with none of them
+// set the output is byte-identical):
+//   FASTKMER_CLI_MIN_COUNT / FASTKMER_CLI_MAX_COUNT  with write = 1 the bin files hold only the
+//       k-mers with min <= count <= max (fk_write_bins_range; defaults 1 / no upper bound)
+//   FASTKMER_CLI_SPECTRUM=<n>  writes <outputDir>/spectrum.txt, "<c>\t<distinct k-mers>\n" for the
+//       nonzero entries of the n-entry abundance spectrum, ascending; the last entry (count >= n - 1)
+//       as ">=<n - 1>\t..."; written whether or not write is set
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -41,6 +49,22 @@ static bool parse_int(const char *s, int *out) {
     return true;
 }
 
+// an optional unsigned environment value in [lo, hi]; false (with a message) when set and malformed
+static bool env_u64(const char *name, uint64_t lo, uint64_t hi, bool *set, uint64_t *out) {
+    const char *v = getenv(name);
+    *set = v && v[0];
+    if (!*set) return true;
+    char *end = nullptr;
+    const unsigned long long x = strtoull(v, &end, 10);
+    if (*end || v[0] == '-' || x < lo || x > hi) {
+        fprintf(stderr, "invalid configuration: %s=%s is not an integer in [%llu, %llu]\n", name, v,
+                (unsigned long long)lo, (unsigned long long)hi);
+        return false;
+    }
+    *out = x;
+    return true;
+}
+
 int main(int argc, char **argv) {
     int a = 1;
     std::string driver = "LocalTestKmerCounter";
@@ -70,6 +94,17 @@ int main(int argc, char **argv) {
         fprintf(stderr, "invalid configuration: %s\n", fk_last_error());
         return 1;
     }
+    bool has_min, has_max, has_spec;
+    uint64_t min_count = 1, max_count = UINT32_MAX, spec_n = 0;
+    if (!env_u64("FASTKMER_CLI_MIN_COUNT", 1, UINT32_MAX, &has_min, &min_count) ||
+        !env_u64("FASTKMER_CLI_MAX_COUNT", 1, UINT32_MAX, &has_max, &max_count) ||
+        !env_u64("FASTKMER_CLI_SPECTRUM", 2, 1ull << 28, &has_spec, &spec_n))
+        return 1;
+    if (min_count > max_count) {
+        fprintf(stderr, "invalid configuration: FASTKMER_CLI_MIN_COUNT > FASTKMER_CLI_MAX_COUNT\n");
+        return 1;
+    }
+    const bool ranged = has_min || has_max;
     char outdir[4096];
     fk_output_dir(&cfg, output, prefix, outdir, sizeof(outdir));
     // TestConfiguration.toString (test/package.scala:37-39)
@@ -141,12 +176,40 @@ int main(int argc, char **argv) {
            cfg.use_ht ? "HT" : "", st.ms_partition, st.ms_count, (unsigned long long)st.distinct,
            std::chrono::duration<double, std::milli>(t1 - t0).count());
     if (cfg.write) {
-        if (fk_write_bins(ctx, outdir) != FK_OK) {
-            fprintf(stderr, "fk_write_bins: %s\n", fk_last_error());
+        const int wrc = ranged ? fk_write_bins_range(ctx, outdir, (uint32_t)min_count, (uint32_t)max_count)
+                               : fk_write_bins(ctx, outdir);
+        if (wrc != FK_OK) {
+            fprintf(stderr, "%s: %s\n", ranged ? "fk_write_bins_range" : "fk_write_bins", fk_last_error());
             fk_destroy(ctx);
             return 1;
         }
         printf("Output written to %s\n", outdir);
+    }
+    if (has_spec) {
+        std::vector<uint64_t> hist((size_t)spec_n, 0);
+        if (fk_spectrum(ctx, hist.data(), hist.size(), nullptr) != FK_OK) {
+            fprintf(stderr, "fk_spectrum: %s\n", fk_last_error());
+            fk_destroy(ctx);
+            return 1;
+        }
+        // the output directory exists only once bin files were written into it
+        std::string dir(outdir);
+        for (size_t i = 1; i <= dir.size(); ++i)
+            if (i == dir.size() || dir[i] == '/') (void)mkdir(dir.substr(0, i).c_str(), 0755);
+        const std::string path = dir + (dir.empty() || dir.back() == '/' ? "" : "/") + "spectrum.txt";
+        FILE *f = fopen(path.c_str(), "w");
+        bool ok = f != nullptr;
+        for (size_t c = 1; ok && c < hist.size(); ++c) {
+            if (!hist[c]) continue;
+            ok = fprintf(f, "%s%zu\t%llu\n", c + 1 == hist.size() ? ">=" : "", c, (unsigned long long)hist[c]) > 0;
+        }
+        if (f && fclose(f) != 0) ok = false;
+        if (!ok) {
+            fprintf(stderr, "cannot write %s\n", path.c_str());
+            fk_destroy(ctx);
+            return 1;
+        }
+        printf("Spectrum written to %s\n", path.c_str());
     }
     fk_destroy(ctx);
     return 0;

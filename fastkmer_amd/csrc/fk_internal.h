@@ -336,6 +336,22 @@ hipError_t launch_query(int KW, const QueryTables &t, const uint64_t *keys, uint
 hipError_t launch_query_seq(int KW, const QueryTables &t, const uint8_t *seq, uint64_t nwin, uint32_t *counts,
                             hipStream_t s);
 
+// ---- abundance spectrum and count-range views of the bucket-major result (fk_spectrum.inc); the
+// arrays are QueryTables' buckets / dense_off / keys / counts, for either count mode
+// hist[0, n) and *tail (tail may be null) overwritten: hist[c] = distinct k-mers of count c for c < n - 1,
+// hist[n - 1] = those of count >= n - 1, *tail = the sum of their counts; n >= 2; distinct = the k-mers
+// of the whole result (an upper bound will do: it picks the width of the LDS table's entries)
+hipError_t launch_spectrum(const uint32_t *counts, const Bucket *buckets, const uint64_t *dense_off,
+                           uint64_t nbuckets, uint64_t distinct, uint64_t *hist, uint64_t n, uint64_t *tail,
+                           hipStream_t s);
+// kept[q] = k-mers of bucket q with lo <= count <= hi
+hipError_t launch_range_count(const uint32_t *counts, const Bucket *buckets, const uint64_t *dense_off,
+                              uint64_t nbuckets, uint32_t lo, uint32_t hi, uint64_t *kept, hipStream_t s);
+// ... written in the bucket's order at keep_off[q] (the exclusive scan of kept, nbuckets + 1 entries)
+hipError_t launch_range_compact(int KW, const uint64_t *out_keys, const uint32_t *out_counts, const Bucket *buckets,
+                                const uint64_t *dense_off, const uint64_t *keep_off, uint64_t nbuckets, uint32_t lo,
+                                uint32_t hi, uint64_t *fkeys, uint32_t *fcounts, hipStream_t s);
+
 // ---- test hook: the 128-bit wave tier's fingerprints cut to `bits` low bits (0: whole), current device
 hipError_t set_fingerprint_bits(int bits);
 

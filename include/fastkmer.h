@@ -326,6 +326,48 @@ int fk_query(fk_ctx *ctx, const uint64_t *keys, size_t n, uint32_t *counts, int3
 int fk_query_device(fk_ctx *ctx, const void *d_keys, size_t n, void *d_counts, void *d_bins);
 int fk_query_sequence(fk_ctx *ctx, const uint8_t *seq, size_t len, uint32_t *counts, size_t cap, size_t *n);
 
+/* ---- abundance spectrum and count ranges (no reference counterpart) ----
+ * What a k-mer count is used for first: the histogram "how many distinct
+ * k-mers occur c times" (jellyfish histo, kmc_tools histogram), and output
+ * with count cut-offs (-ci / -cx, -L / -U: drop the singletons, keep counts in
+ * [lo, hi]).  Both are computed on the device from the counted result, for
+ * use_ht == 0 and use_ht == 1 alike; the calls read the result only:
+ * fk_get_bin, fk_write_bins and fk_query answer the same before and after
+ * them.  They need a result (FK_E_STATE before fk_finish / fk_reduce and after
+ * a new job's first fk_ingest); an empty job answers with zeros and writes no
+ * files.  None of them is collective.
+ *   fk_spectrum: hist has n >= 2 entries (else FK_E_INVALID).  hist[0] = 0;
+ *     hist[c], 1 <= c <= n - 2: the distinct canonical k-mers this rank owns
+ *     with count exactly c; hist[n - 1]: those with count >= n - 1, and
+ *     *tail_kmers (may be NULL) the sum of their counts.  So the sum of hist is
+ *     the rank's distinct k-mers (fk_stats.distinct), and the sum of
+ *     c * hist[c] over c < n - 1 plus *tail_kmers its counted k-mer windows.
+ *     The job's spectrum is the sum of the ranks': fk_comm_allreduce_u64 on
+ *     hist (and on tail_kmers) gives it.
+ *   fk_spectrum_device: pointers on the context's device (d_hist uint64[n],
+ *     d_tail_kmers uint64[1] or NULL); only queues the work on the context's
+ *     stream (the caller's after fk_set_stream): no allocation, no
+ *     synchronisation.  The outputs are overwritten, not accumulated into.
+ * Count ranges: a k-mer is kept when min_count <= count <= max_count, both
+ * ends inclusive; max_count = UINT32_MAX: no upper bound.  FK_E_INVALID for
+ * min_count == 0 or min_count > max_count.  (1, UINT32_MAX) gives exactly what
+ * fk_bin_sizes / fk_get_bin / fk_write_bins give.
+ *   fk_bin_sizes_range: kept k-mers per bin, all b bins (0 for bins owned by
+ *     other ranks).
+ *   fk_get_bin_range: fk_get_bin's order with the other k-mers removed
+ *     (ascending for use_ht == 0, table order for use_ht == 1) and its buffer
+ *     rules: *n is always set, FK_E_RANGE when cap < *n or the bin is out of
+ *     [0, b); keys and counts may each be NULL.
+ *   fk_write_bins_range: <out_dir>/bin<b> files of the kept lines only, "EOF"
+ *     after the last kept line when use_ht == 0; a bin with no kept line gets
+ *     no file, as an empty bin gets none from fk_write_bins. */
+int fk_spectrum(fk_ctx *ctx, uint64_t *hist, size_t n, uint64_t *tail_kmers);
+int fk_spectrum_device(fk_ctx *ctx, void *d_hist, size_t n, void *d_tail_kmers);
+int fk_bin_sizes_range(fk_ctx *ctx, uint32_t min_count, uint32_t max_count, uint64_t *distinct_per_bin);
+int fk_get_bin_range(fk_ctx *ctx, int32_t bin, uint32_t min_count, uint32_t max_count,
+                     uint64_t *keys, uint32_t *counts, size_t cap, size_t *n);
+int fk_write_bins_range(fk_ctx *ctx, const char *out_dir, uint32_t min_count, uint32_t max_count);
+
 /* ---- test hook (no reference counterpart) ----
  * One bucket through the wave-tier count kernel on `device`: the n keys
  * (k <= 32: one word each, n <= 512; 33 <= k <= 63: (hi, lo) pairs, n <= 256)

@@ -161,6 +161,46 @@ JNIEXPORT void JNICALL Java_skc_gpu_NativeKmerCounter_00024_writeBins(JNIEnv *en
     if (rc != FK_OK) throw_fk(env, rc);
 }
 
+/* def spectrum(h, n): Array[Long] -- the abundance spectrum of this rank's k-mers: entry c = distinct
+ * k-mers with count c, the last entry those with count >= n - 1 (sum the ranks' arrays for the job's) */
+JNIEXPORT jlongArray JNICALL Java_skc_gpu_NativeKmerCounter_00024_spectrum(JNIEnv *env, jobject self, jlong h,
+                                                                          jint n) {
+    (void)self;
+    if (n < 2) {
+        jclass ex = (*env)->FindClass(env, "java/lang/IllegalArgumentException");
+        if (ex) (*env)->ThrowNew(env, ex, "a spectrum has n >= 2 entries");
+        return NULL;
+    }
+    jlongArray out = (*env)->NewLongArray(env, n);
+    if (!out) return out;
+    jlong *dst = (*env)->GetLongArrayElements(env, out, NULL);
+    if (!dst) return NULL;
+    const int rc = fk_spectrum(ctx_of(h), (uint64_t *)dst, (size_t)n, NULL);
+    (*env)->ReleaseLongArrayElements(env, out, dst, 0);
+    if (rc != FK_OK) throw_fk(env, rc);
+    return out;
+}
+
+/* def writeBinsRange(h, outDir, minCount, maxCount): Unit -- bin<b> files of the k-mers with
+ * minCount <= count <= maxCount only (maxCount >= 2^32 - 1: no upper bound) */
+JNIEXPORT void JNICALL Java_skc_gpu_NativeKmerCounter_00024_writeBinsRange(JNIEnv *env, jobject self, jlong h,
+                                                                          jstring dir, jlong min_count,
+                                                                          jlong max_count) {
+    (void)self;
+    if (min_count < 1 || max_count < min_count) {
+        jclass ex = (*env)->FindClass(env, "java/lang/IllegalArgumentException");
+        if (ex) (*env)->ThrowNew(env, ex, "writeBinsRange needs 1 <= minCount <= maxCount");
+        return;
+    }
+    const char *d = (*env)->GetStringUTFChars(env, dir, NULL);
+    if (!d) return;
+    const uint32_t lo = min_count > (jlong)UINT32_MAX ? UINT32_MAX : (uint32_t)min_count;
+    const uint32_t hi = max_count > (jlong)UINT32_MAX ? UINT32_MAX : (uint32_t)max_count;
+    const int rc = fk_write_bins_range(ctx_of(h), d, lo, hi);
+    (*env)->ReleaseStringUTFChars(env, dir, d);
+    if (rc != FK_OK) throw_fk(env, rc);
+}
+
 /* def findBinSignatures(h, outDir): Unit -- executeFindBinSignaturesJob's
  * bin_signatures<b>.txt files (SBKC:956-986) for this context's input */
 JNIEXPORT void JNICALL Java_skc_gpu_NativeKmerCounter_00024_findBinSignatures(JNIEnv *env, jobject self, jlong h,

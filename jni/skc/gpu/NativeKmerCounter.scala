@@ -26,6 +26,11 @@ object NativeKmerCounter {
   @native def commInit(h: Long, id: Array[Byte]): Unit
   @native def binSizes(h: Long): Array[Long]
   @native def writeBins(h: Long, outDir: String): Unit
+  /** Abundance spectrum of this rank's k-mers: entry c = distinct k-mers of count c, the last
+    * entry those of count >= n - 1; the job's spectrum is the sum of the ranks' arrays. */
+  @native def spectrum(h: Long, n: Int): Array[Long]
+  /** writeBins for the k-mers with minCount <= count <= maxCount (0xFFFFFFFFL: no upper bound). */
+  @native def writeBinsRange(h: Long, outDir: String, minCount: Long, maxCount: Long): Unit
   @native def findBinSignatures(h: Long, outDir: String): Unit
   @native def destroy(h: Long): Unit
 
