@@ -122,6 +122,12 @@ def lib():
         "fk_ingest_reserve": (ctypes.c_int, [P, U64]),
         "fk_split_bytes": (ctypes.c_int, [ctypes.c_char_p, I32, I32, I32, I32, P, SZ, ctypes.POINTER(SZ)]),
         "fk_ingest_file_range": (ctypes.c_int, [P, ctypes.c_char_p, I32, I32, U64]),
+        "fk_set_input_format": (ctypes.c_int, [P, I32, I32, I32]),
+        "fk_input_format": (ctypes.c_int, [P, ctypes.POINTER(I32), ctypes.POINTER(I32), ctypes.POINTER(I32)]),
+        "fk_fastq_info": (ctypes.c_int, [P, P]),
+        "fk_debug_fastq_ms": (ctypes.c_int, [P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(U64)]),
+        "fk_fastq_frontier": (ctypes.c_int, [ctypes.c_char_p, SZ, ctypes.POINTER(SZ)]),
+        "fk_split_bytes_fastq": (ctypes.c_int, [ctypes.c_char_p, I32, I32, P, SZ, ctypes.POINTER(SZ)]),
         "fk_synth_fasta_device": (ctypes.c_int, [P, U64, U64, I32, U64, U64, ctypes.c_double, ctypes.c_double]),
         "fk_synth_fasta_to_device": (ctypes.c_int, [P, U64, U64, I32, U64, U64, ctypes.c_double, ctypes.c_double]),
         "fk_map": (ctypes.c_int, [P, P]),
@@ -244,6 +250,30 @@ def split_bytes(path: str, world: int, rank: int, k: int, sequence_type: int = 0
     return buf.raw[:n.value]
 
 
+FORMATS = {"fasta": 0, "fastq": 1}  # FK_FORMAT_*
+
+
+def split_bytes_fastq(path: str, world: int, rank: int) -> bytes:
+    """The bytes rank `rank` of `world` ingests from the FASTQ file at `path` (fk_split_bytes_fastq:
+    the whole records whose '@' line starts in the rank's byte range; host only)."""
+    L = lib()
+    n = ctypes.c_size_t()
+    p = os.fsencode(path)
+    _check(L.fk_split_bytes_fastq(p, world, rank, None, 0, ctypes.byref(n)))
+    buf = ctypes.create_string_buffer(max(n.value, 1))
+    _check(L.fk_split_bytes_fastq(p, world, rank, buf, n.value, ctypes.byref(n)))
+    return buf.raw[:n.value]
+
+
+def fastq_frontier(buf: bytes) -> int:
+    """fk_fastq_frontier: the start of the last FASTQ record of buf whose '@' line and '+' line both
+    begin inside it (buf[0] counts as a line start); len(buf) when there is none.  Host only."""
+    raw = bytes(buf)
+    off = ctypes.c_size_t()
+    _check(lib().fk_fastq_frontier(raw, len(raw), ctypes.byref(off)))
+    return off.value
+
+
 def decode_keys(keys: np.ndarray, k: int) -> list[str]:
     """2-bit keys (one word for k <= 32, (hi, lo) pairs for k > 32) -> strings."""
     out = []
@@ -331,8 +361,11 @@ class KmerCounter:
     """Device-resident exact canonical k-mer counter for one rank."""
 
     def __init__(self, k: int, m: int, x: int = 3, B: int = 2048, use_ht: bool = False, sequence_type: int = 0,
-                 n_ranks: int = 1, rank: int = 0, device: int = -1):
+                 n_ranks: int = 1, rank: int = 0, device: int = -1, input_format: str = "fasta",
+                 min_quality: int = 0, quality_offset: int = 33):
         L = lib()
+        if input_format not in FORMATS:
+            raise ValueError(f"input_format must be one of {sorted(FORMATS)}")
         self.k, self.m, self.x, self.use_ht = k, m, x, bool(use_ht)
         self.n_ranks, self.rank = n_ranks, rank
         self._cfg = make_config(k, m, x, B, use_ht, sequence_type, False, n_ranks, rank, device)
@@ -344,6 +377,12 @@ class KmerCounter:
         self.record_bytes = L.fk_record_bytes(h)
         self._keep = None
         self._sizes = None
+        if (input_format, min_quality, quality_offset) != ("fasta", 0, 33):
+            try:
+                self.set_input_format(input_format, min_quality, quality_offset)
+            except Exception:
+                self.close()
+                raise
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -363,6 +402,36 @@ class KmerCounter:
         self.close()
 
     # -- input
+    def set_input_format(self, input_format: str = "fasta", min_quality: int = 0, quality_offset: int = 33) -> None:
+        """The format of the next jobs' input (fk_set_input_format; between jobs only): "fasta", or
+        "fastq" with bases of Phred score below min_quality counted as N (0: qualities ignored) under
+        quality_offset 33 or 64."""
+        if input_format not in FORMATS:
+            raise ValueError(f"input_format must be one of {sorted(FORMATS)}")
+        _check(lib().fk_set_input_format(self._h, FORMATS[input_format], int(min_quality), int(quality_offset)))
+
+    def input_format(self) -> tuple:
+        """(input_format, min_quality, quality_offset) as set."""
+        f, q, o = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        _check(lib().fk_input_format(self._h, ctypes.byref(f), ctypes.byref(q), ctypes.byref(o)))
+        return {v: n for n, v in FORMATS.items()}[f.value], q.value, o.value
+
+    def fastq_info(self) -> dict:
+        """After map() / finish() of a FASTQ job (also a failed one): its records, the bases masked by
+        min_quality, and the index of the first malformed record (None: none)."""
+        out = (ctypes.c_uint64 * 3)()
+        _check(lib().fk_fastq_info(self._h, out))
+        bad = int(out[2])
+        return {"records": int(out[0]), "masked_bases": int(out[1]),
+                "first_malformed": None if bad == 0xFFFFFFFFFFFFFFFF else bad}
+
+    def fastq_stage_ms(self) -> tuple:
+        """Measurement hook (fk_debug_fastq_ms): (device ms summed over the last FASTQ job's normalise
+        launches, their number)."""
+        ms, n = ctypes.c_double(), ctypes.c_uint64()
+        _check(lib().fk_debug_fastq_ms(self._h, ctypes.byref(ms), ctypes.byref(n)))
+        return ms.value, n.value
+
     def ingest(self, fasta: bytes) -> None:
         self._keep = bytes(fasta)
         _check(lib().fk_ingest(self._h, self._keep, len(self._keep), 1))
@@ -688,17 +757,20 @@ def lpt_owners(sizes, n_ranks: int) -> np.ndarray:
     return owner
 
 
-def execute_job(configuration: TestConfiguration) -> KmerCounter:
+def execute_job(configuration: TestConfiguration, input_format: str = "fasta", min_quality: int = 0,
+                quality_offset: int = 33) -> KmerCounter:
     """SparkBinKmerCounter.executeJob (SparkBinKmerCounter.scala:989-1046) on one GPU.
 
     Reads the dataset, counts, and writes ``configuration.outputDir/bin<b>``
     when ``configuration.write`` is set.  Returns the counter (results stay
-    device resident until it is closed).
+    device resident until it is closed).  ``input_format="fastq"`` reads a FASTQ
+    dataset (KmerCounter.set_input_format).
     """
     with open(configuration.dataset, "rb") as f:
         data = f.read()
     kc = KmerCounter(configuration.k, configuration.m, configuration.x, configuration.max_b,
-                     configuration.useHT, configuration.sequenceType)
+                     configuration.useHT, configuration.sequenceType, input_format=input_format,
+                     min_quality=min_quality, quality_offset=quality_offset)
     kc.ingest(data)
     kc.finish()
     if configuration.write:

@@ -316,6 +316,20 @@ struct fk_ctx {
     const uint8_t *d_fasta = nullptr;
     uint64_t n_fasta = 0;
     DevBuf fasta_own;
+    // FASTQ input (fk_set_input_format): the device input is normalised in place to text the FASTA
+    // parsers read (fk_fastq.inc), record-aligned range after range, each byte once
+    int32_t in_format = FK_FORMAT_FASTA, fq_min_q = 0, fq_q_off = 33;  // the next job's
+    bool job_open = false;      // between a job's first ingest and its fk_map / fk_finish
+    bool fq_job = false;        // the current input is FASTQ
+    uint64_t fq_done = 0;       // the frontier: bytes [0, fq_done) are normalised (and may be mapped)
+    std::vector<uint8_t> fq_tail;  // host copy of the caller's bytes [fq_done, n_fasta) (a record straddling two calls)
+    bool fq_launched = false;   // a normalise launch of this job has been queued
+    DevBuf fq_ws, fq_info;      // launch workspace; the job's records, masked bases, ~(first bad record), overflow
+    PinBuf fq_pin;              // fq_info read back with the map's counters
+    bool fq_have_info = false;  // fk_fastq_info has figures (a FASTQ job was mapped)
+    uint64_t fq_out[3] = {0, 0, UINT64_MAX};
+    std::vector<hipEvent_t> fq_evs;  // begin / end of every normalise launch of the job (fk_debug_fastq_ms)
+    size_t fq_nev = 0;
 
     // parse + encode
     DevBuf tile_last_nl, tile_off, npos_dev, codes, valid;
@@ -714,6 +728,11 @@ FK_EXPORT void fk_destroy(fk_ctx *c) {
                       &c->q_in, &c->q_counts, &c->q_bins, &c->sp_hist, &c->rg_kept, &c->rg_off,
                       &c->sp_base, &c->sp_keys, &c->sp_subs, &c->sp_par, &c->sp_fb, &c->mid_fb};
     for (DevBuf *b : bufs) release(*b);
+    release(c->fq_ws);
+    release(c->fq_info);
+    for (auto &e : c->fq_evs)
+        if (e) (void)hipEventDestroy(e);
+    c->fq_pin.release();
     for (int i = 0; i < 2; ++i) {
         if (c->pinned[i]) (void)hipHostFree(c->pinned[i]);
         if (c->pin_ev[i]) (void)hipEventDestroy(c->pin_ev[i]);
@@ -812,6 +831,146 @@ static int grow_keep(DevBuf &b, size_t bytes, size_t keep, hipStream_t s) {
     return FK_OK;
 }
 
+// ---- FASTQ input: the device stage in front of the FASTA parsers (fk_fastq.inc)
+
+FK_EXPORT int fk_set_input_format(fk_ctx *c, int32_t format, int32_t min_quality, int32_t quality_offset) {
+    if (!c) return set_err(FK_E_INVALID, "null ctx");
+    if (c->job_open) return set_err(FK_E_STATE, "fk_set_input_format inside a job (after its first fk_ingest)");
+    if (format != FK_FORMAT_FASTA && format != FK_FORMAT_FASTQ) return set_err(FK_E_INVALID, "unknown input format %d", format);
+    if (quality_offset != 33 && quality_offset != 64)
+        return set_err(FK_E_INVALID, "quality_offset must be 33 or 64, got %d", quality_offset);
+    if (min_quality < 0 || min_quality > 93) return set_err(FK_E_INVALID, "min_quality must be in 0..93, got %d", min_quality);
+    if (format == FK_FORMAT_FASTQ && c->cfg.sequence_type != 0)
+        return set_err(FK_E_INVALID, "FASTQ input needs sequence_type 0 (short reads)");
+    c->in_format = format;
+    c->fq_min_q = min_quality;
+    c->fq_q_off = quality_offset;
+    return FK_OK;
+}
+
+FK_EXPORT int fk_input_format(const fk_ctx *c, int32_t *format, int32_t *min_quality, int32_t *quality_offset) {
+    if (!c) return set_err(FK_E_INVALID, "null ctx");
+    if (format) *format = c->in_format;
+    if (min_quality) *min_quality = c->fq_min_q;
+    if (quality_offset) *quality_offset = c->fq_q_off;
+    return FK_OK;
+}
+
+FK_EXPORT int fk_fastq_info(fk_ctx *c, uint64_t out[3]) {
+    if (!c || !out) return set_err(FK_E_INVALID, "null argument");
+    if (!c->fq_have_info) return set_err(FK_E_STATE, "fk_fastq_info before the fk_map / fk_finish of a FASTQ job");
+    for (int i = 0; i < 3; ++i) out[i] = c->fq_out[i];
+    return FK_OK;
+}
+
+FK_EXPORT int fk_debug_fastq_ms(fk_ctx *c, double *ms, uint64_t *launches) {
+    if (!c || !ms || !launches) return set_err(FK_E_INVALID, "null argument");
+    if (!c->fq_have_info || c->job_open) return set_err(FK_E_STATE, "fk_debug_fastq_ms before the fk_map / fk_finish of a FASTQ job");
+    DeviceGuard dg_(c->device);
+    double sum = 0.0;
+    for (size_t i = 0; i + 1 < c->fq_nev; i += 2) sum += ev_ms(c->fq_evs[i], c->fq_evs[i + 1]);
+    *ms = sum;
+    *launches = c->fq_nev / 2;
+    return FK_OK;
+}
+
+FK_EXPORT int fk_fastq_frontier(const uint8_t *buf, size_t n, size_t *off) {
+    if ((!buf && n) || !off) return set_err(FK_E_INVALID, "null argument");
+    *off = (size_t)fastq_frontier_scan([buf](uint64_t p) { return buf[p]; }, 0, n);
+    return FK_OK;
+}
+
+// A job's first ingest: the format is the job's from here on.
+static int fq_begin_job(fk_ctx *c, bool fastq) {
+    c->job_open = true;
+    c->fq_job = fastq;
+    c->fq_done = 0;
+    c->fq_tail.clear();
+    c->fq_launched = false;
+    c->fq_nev = 0;
+    if (!fastq) return FK_OK;
+    FK_TRY(ensure(c->fq_info, 32));
+    if (c->fq_pin.ensure(32)) return set_err(FK_E_NOMEM, "hipHostMalloc(32) failed");
+    HIP_TRY(hipMemsetAsync(c->fq_info.p, 0, 32, c->stream));
+    return FK_OK;
+}
+
+// Queues the normalisation of the record-aligned range [a, b) of fasta_own on the map stream
+// (src: the bytes come from src[a, b), a borrowed input); final_: the input ends at b.
+static int fq_normalise(fk_ctx *c, const uint8_t *src, uint64_t a, uint64_t b, bool final_) {
+    if (b <= a) return FK_OK;
+    if (b - a >= (1ull << 32))
+        return set_err(FK_E_INVALID, "FASTQ: %llu bytes in one normalise range (a record, or a device input, of 4 GiB or more)",
+                       (unsigned long long)(b - a));
+    FK_TRY(ensure(c->fq_ws, fastq_ws_bytes(b - a)));
+    while (c->fq_evs.size() < c->fq_nev + 2) {
+        hipEvent_t e = nullptr;
+        HIP_TRY(hipEventCreate(&e));
+        c->fq_evs.push_back(e);
+    }
+    HIP_TRY(hipEventRecord(c->fq_evs[c->fq_nev], c->stream));
+    HIP_TRY(launch_fastq_normalise(c->fasta_own.as<uint8_t>(), src, a, b, final_ ? 1 : 0, c->fq_min_q, c->fq_q_off,
+                                   c->fq_ws.p, c->fq_info.as<unsigned long long>(), c->stream));
+    HIP_TRY(hipEventRecord(c->fq_evs[c->fq_nev + 1], c->stream));
+    c->fq_nev += 2;
+    c->fq_launched = true;
+    return FK_OK;
+}
+
+// The caller's bytes src[0, off) of this fk_ingest call have landed behind the `have` bytes of
+// earlier calls: moves the frontier to the start of the last record not yet known to be complete
+// (the input's end with final_), queues the normalisation up to it, and returns it in *limit --
+// the map may read below it.  The host looks at the last few lines before have + off only.
+static int fq_advance(fk_ctx *c, const uint8_t *src, uint64_t have, uint64_t off, bool final_, uint64_t *limit) {
+    const uint64_t end = have + off;
+    uint64_t f = end;
+    if (!final_) {
+        const uint64_t tb = have - c->fq_tail.size();  // fq_tail holds [tb, have), tb <= fq_done
+        const std::vector<uint8_t> &tail = c->fq_tail;
+        // at most FQ_LOOK bytes back: a record longer than that moves the frontier once the next one is seen
+        constexpr uint64_t FQ_LOOK = 16ull << 20;
+        f = fastq_frontier_scan([&](uint64_t p) { return p < have ? tail[p - tb] : src[p - have]; }, c->fq_done, end,
+                                end > FQ_LOOK ? end - FQ_LOOK : 0);
+        if (f == end) f = c->fq_done;  // no record start in sight (a long read): the frontier stays
+    }
+    FK_TRY(fq_normalise(c, nullptr, c->fq_done, f, final_));
+    c->fq_done = f;
+    *limit = f;
+    return FK_OK;
+}
+
+// fk_map / fk_signature_counts: what no fk_ingest(..., last = 1) has normalised ends the input.
+static int fq_finish_pending(fk_ctx *c, uint64_t n) {
+    if (!c->fq_job || c->fq_done >= n) return FK_OK;
+    FK_TRY(fq_normalise(c, nullptr, c->fq_done, n, true));
+    c->fq_done = n;
+    c->fq_tail.clear();
+    return FK_OK;
+}
+
+// Queues the read-back of the job's FASTQ counters behind the normalise launches (the caller's next
+// wait on the map stream covers it) / reads them: FK_E_INVALID for a malformed record.
+static int fq_info_queue(fk_ctx *c) {
+    if (c->fq_job && c->fq_launched)
+        HIP_TRY(hipMemcpyAsync(c->fq_pin.p, c->fq_info.p, 32, hipMemcpyDeviceToHost, c->stream));
+    return FK_OK;
+}
+static int fq_info_read(fk_ctx *c) {
+    if (!c->fq_job) return FK_OK;
+    const uint64_t *h = c->fq_pin.as<uint64_t>();
+    const bool any = c->fq_launched;
+    c->fq_out[0] = any ? h[0] : 0;
+    c->fq_out[1] = any ? h[1] : 0;
+    c->fq_out[2] = any && h[2] ? ~h[2] : UINT64_MAX;
+    c->fq_have_info = true;
+    if (any && h[3])
+        return set_err(FK_E_INVALID, "FASTQ: more than one line per 4 bytes over a range of the input (the line index overflowed)");
+    if (c->fq_out[2] != UINT64_MAX)
+        return set_err(FK_E_INVALID, "FASTQ record %llu is malformed (no '@' or '+' line, quality and sequence of "
+                                     "different lengths, or the input ends inside it)", (unsigned long long)c->fq_out[2]);
+    return FK_OK;
+}
+
 static bool premap_eligible(const fk_ctx *c) {
     return c->fused && map_fused_supported(c->cfg.k, c->cfg.m, (uint32_t)c->Bc);
 }
@@ -900,6 +1059,7 @@ static int ingest_impl(fk_ctx *c, const uint8_t *fasta, size_t n, int last) {
         c->pm_active = premap_eligible(c);
         c->pm_tiles = 0;
         c->pm_last_seen = false;
+        FK_TRY(fq_begin_job(c, c->in_format == FK_FORMAT_FASTQ));
     } else if (c->pm_last_seen) {
         c->pm_active = false;  // appending after the final tiles: fk_map maps the whole input
     }
@@ -909,6 +1069,10 @@ static int ingest_impl(fk_ctx *c, const uint8_t *fasta, size_t n, int last) {
         FK_TRY(grow_keep(c->fasta_own, need, have, s));
     }
     c->d_fasta = c->fasta_own.as<uint8_t>();
+    // FASTQ: every segment is normalised up to the frontier before the map may read it; the map's
+    // limit is the frontier where it is `landed` for FASTA
+    const bool fq = c->fq_job;
+    if (fq) FK_TRY(ensure(c->fq_ws, fastq_ws_bytes(std::min<uint64_t>(n, 4 * c->ingest_seg) + (1u << 20))));
     if (c->pm_active) {
         // record slots and per-tile counts of every tile this input can hold (kept on growth)
         const uint64_t tiles = (need + fm_tile_bytes(FUSED_NT) - 1) / fm_tile_bytes(FUSED_NT) + 1;
@@ -972,7 +1136,7 @@ static int ingest_impl(fk_ctx *c, const uint8_t *fasta, size_t n, int last) {
         const size_t nseg = (n + seg - 1) / seg;
         const size_t small_from = n - std::min(n, std::max<size_t>(n / 10, 4 * seg));
         auto seg_len = [&](size_t off) { return std::min(off < small_from ? big : seg, n - off); };
-        while (c->pm_active && c->seg_evs.size() < nseg) {
+        while ((c->pm_active || fq) && c->seg_evs.size() < nseg) {
             hipEvent_t e = nullptr;
             HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
             c->seg_evs.push_back(e);
@@ -981,7 +1145,7 @@ static int ingest_impl(fk_ctx *c, const uint8_t *fasta, size_t n, int last) {
         for (size_t i = 0; off < n; ++i) {
             const size_t len = seg_len(off);
             HIP_TRY(hipMemcpyAsync(dst + off, fasta + off, len, hipMemcpyHostToDevice, cs));
-            if (c->pm_active) HIP_TRY(hipEventRecord(c->seg_evs[i], cs));
+            if (c->pm_active || fq) HIP_TRY(hipEventRecord(c->seg_evs[i], cs));
             off += len;
         }
         HIP_TRY(hipEventRecord(c->h2d_ev[1], cs));
@@ -995,10 +1159,13 @@ static int ingest_impl(fk_ctx *c, const uint8_t *fasta, size_t n, int last) {
         }
         c->seg_tiles.clear();
         off = 0;
-        for (size_t i = 0; c->pm_active && off < n; ++i) {
+        for (size_t i = 0; (c->pm_active || fq) && off < n; ++i) {
             off += seg_len(off);
             HIP_TRY(hipStreamWaitEvent(s, c->seg_evs[i], 0));
-            FK_TRY(premap_launch(c, have + off, last && off == n));
+            uint64_t limit = have + off;
+            if (fq) FK_TRY(fq_advance(c, fasta, have, off, last && off == n, &limit));
+            if (!c->pm_active) continue;
+            FK_TRY(premap_launch(c, limit, last && off == n));
             if (pieces) {
                 FK_TRY(xch_maybe_piece(c));
             } else {
@@ -1017,10 +1184,13 @@ static int ingest_impl(fk_ctx *c, const uint8_t *fasta, size_t n, int last) {
             HIP_TRY(hipMemcpyAsync(dst + off, c->pinned[i & 1], len, hipMemcpyHostToDevice, cs));
             HIP_TRY(hipEventRecord(c->pin_ev[i & 1], cs));
             off += len;
-            if (c->pm_active) {
+            if (c->pm_active || fq) {
                 HIP_TRY(hipEventRecord(c->seg_ev, cs));
                 HIP_TRY(hipStreamWaitEvent(s, c->seg_ev, 0));
-                FK_TRY(premap_launch(c, have + off, last && off == n));
+                uint64_t limit = have + off;
+                if (fq) FK_TRY(fq_advance(c, fasta, have, off, last && off == n, &limit));
+                if (!c->pm_active) continue;
+                FK_TRY(premap_launch(c, limit, last && off == n));
                 if (pieces) {
                     FK_TRY(xch_maybe_piece(c));
                 } else {
@@ -1030,6 +1200,17 @@ static int ingest_impl(fk_ctx *c, const uint8_t *fasta, size_t n, int last) {
             }
         }
         HIP_TRY(hipEventRecord(c->h2d_ev[1], cs));
+    }
+    if (fq) {
+        uint64_t limit = 0;
+        if (last && n == 0) FK_TRY(fq_advance(c, fasta, have, 0, true, &limit));  // the input ends here
+        // the caller's bytes behind the frontier, for the next call's look at the record they begin
+        const uint64_t tb = have - c->fq_tail.size();
+        std::vector<uint8_t> tail;
+        if (c->fq_done < have) tail.assign(c->fq_tail.begin() + (c->fq_done - tb), c->fq_tail.end());
+        const uint64_t from = c->fq_done > have ? c->fq_done - have : 0;
+        if (from < n) tail.insert(tail.end(), fasta + from, fasta + n);
+        c->fq_tail.swap(tail);
     }
     if (c->pm_active && last) {
         c->pm_last_seen = true;
@@ -1083,7 +1264,7 @@ struct Fd {
     }
 };
 int open_split(const char *path, int32_t world, int32_t rank, int32_t k, int32_t seq, Fd &f, uint64_t &size,
-               SplitPlan &plan) {
+               SplitPlan &plan, bool fastq = false) {
     f.fd = open(path, O_RDONLY | O_CLOEXEC);
     if (f.fd < 0) return set_err(FK_E_IO, "open(%s): %s", path, strerror(errno));
     struct stat st {};
@@ -1091,7 +1272,7 @@ int open_split(const char *path, int32_t world, int32_t rank, int32_t k, int32_t
     size = (uint64_t)st.st_size;
     std::string err;
     if (seq != 0 && seq != 1) return set_err(FK_E_INVALID, "sequence_type must be 0 or 1");
-    if (plan_split(f.fd, size, world, rank, k, seq, plan, err))
+    if (fastq ? plan_split_fastq(f.fd, size, world, rank, plan, err) : plan_split(f.fd, size, world, rank, k, seq, plan, err))
         return set_err(world < 1 || rank < 0 || rank >= world || k < 1 ? FK_E_INVALID : FK_E_IO, "%s: %s", path,
                        err.c_str());
     return FK_OK;
@@ -1105,6 +1286,20 @@ FK_EXPORT int fk_split_bytes(const char *path, int32_t world, int32_t rank, int3
     uint64_t size = 0;
     SplitPlan plan;
     FK_TRY(open_split(path, world, rank, k, sequence_type, f, size, plan));
+    *n = (size_t)plan.total;
+    if (!out) return FK_OK;
+    if (cap < plan.total) return set_err(FK_E_RANGE, "split of %llu bytes, buffer holds %zu", (unsigned long long)plan.total, cap);
+    std::string err;
+    if (read_split(f.fd, size, plan, 0, plan.total, out, err)) return set_err(FK_E_IO, "%s: %s", path, err.c_str());
+    return FK_OK;
+}
+
+FK_EXPORT int fk_split_bytes_fastq(const char *path, int32_t world, int32_t rank, uint8_t *out, size_t cap, size_t *n) {
+    if (!path || !n) return set_err(FK_E_INVALID, "null argument");
+    Fd f;
+    uint64_t size = 0;
+    SplitPlan plan;
+    FK_TRY(open_split(path, world, rank, 1, 0, f, size, plan, true));
     *n = (size_t)plan.total;
     if (!out) return FK_OK;
     if (cap < plan.total) return set_err(FK_E_RANGE, "split of %llu bytes, buffer holds %zu", (unsigned long long)plan.total, cap);
@@ -1129,7 +1324,7 @@ static int ingest_file_impl(fk_ctx *c, const char *path, int32_t world, int32_t 
     Fd f;
     uint64_t size = 0;
     SplitPlan plan;
-    FK_TRY(open_split(path, world, rank, c->cfg.k, c->cfg.sequence_type, f, size, plan));
+    FK_TRY(open_split(path, world, rank, c->cfg.k, c->cfg.sequence_type, f, size, plan, c->in_format == FK_FORMAT_FASTQ));
     const uint64_t total = plan.total;
     if (total == 0) return ingest_impl(c, nullptr, 0, 1);
     if (!window) window = 256ull << 20;
@@ -1184,7 +1379,14 @@ static int ingest_device_impl(fk_ctx *c, const void *d, size_t n, int last) {
     c->pm_active = false;
     pieces_reset(c);
     reset_results(c);
-    if (((uintptr_t)d & 15) != 0) {
+    FK_TRY(fq_begin_job(c, c->in_format == FK_FORMAT_FASTQ));
+    if (c->fq_job) {
+        // the borrowed buffer stays as it is: the stage copies it into fasta_own as it reads it
+        FK_TRY(ensure(c->fasta_own, n));
+        FK_TRY(fq_normalise(c, (const uint8_t *)d, 0, n, true));
+        c->fq_done = n;
+        c->d_fasta = c->fasta_own.as<uint8_t>();
+    } else if (((uintptr_t)d & 15) != 0) {
         FK_TRY(ensure(c->fasta_own, n));
         HIP_TRY(hipMemcpyAsync(c->fasta_own.p, d, n, hipMemcpyDeviceToDevice, c->stream));
         c->d_fasta = c->fasta_own.as<uint8_t>();
@@ -1220,6 +1422,7 @@ FK_EXPORT int fk_synth_fasta_device(fk_ctx *c, uint64_t first_read, uint64_t n_r
     c->ingest_fresh = true;
     c->pm_active = false;
     pieces_reset(c);
+    FK_TRY(fq_begin_job(c, false));  // synthetic FASTA, whatever the context's format
     c->d_fasta = c->fasta_own.as<uint8_t>();
     c->n_fasta = nb;
     reset_results(c);
@@ -1304,6 +1507,11 @@ static int map_records(fk_ctx *c) {
     c->stats.fasta_bytes = n;
     c->nrec = c->nkmers = 0;
     c->rec_tiled = false;
+    c->job_open = false;
+    // FASTQ: what is left behind the frontier ends the input; the stage's counters and its malformed
+    // flag come back with the map's own read-back below (every path with input waits on the stream)
+    FK_TRY(fq_finish_pending(c, n));
+    FK_TRY(fq_info_queue(c));
 
     // 0. fused parse + signature (streamed by fk_ingest, or one launch here); the
     // two-kernel path below maps the inputs the fused kernel hands back
@@ -1423,7 +1631,7 @@ static int map_records(fk_ctx *c) {
     c->stats.kmers = c->nkmers;
     c->stats.superkmers = c->nrec;
     c->stats.ms_total += now_ms() - t_start;
-    return FK_OK;
+    return fq_info_read(c);
 }
 
 // Grouped emit: records and k-mers of the mapped records per (destination, local bin) part and the
@@ -3161,6 +3369,8 @@ static int split_sample(const char *path, int32_t world, int32_t rank, int32_t k
 
 FK_EXPORT int fk_balance_bins_file(fk_ctx *c, const char *path, int32_t world, int32_t rank, double fraction) {
     if (!c || !path) return set_err(FK_E_INVALID, "null argument");
+    if (c->in_format == FK_FORMAT_FASTQ)
+        return set_err(FK_E_INVALID, "fk_balance_bins_file reads FASTA only: pass whole FASTQ records to fk_balance_bins");
     std::vector<uint8_t> sample;
     int rc = check_split_rank(c, world, rank, "fk_balance_bins_file");
     if (!rc) rc = split_sample(path, world, rank, c->cfg.k, c->cfg.sequence_type, fraction, sample);
@@ -3739,6 +3949,7 @@ FK_EXPORT int fk_signature_counts(fk_ctx *c, void *d_counts, uint64_t n_counts) 
     hipStream_t s = c->stream;
     const uint64_t n = c->d_fasta ? c->n_fasta : 0;
     HIP_TRY(hipMemsetAsync(d_counts, 0, slots * 8, s));
+    FK_TRY(fq_finish_pending(c, n));  // FASTQ: the input ends here (fk_map reports a malformed record)
     if (n) {
         const uint64_t ntiles = (n + ENC_TILE - 1) / ENC_TILE;
         const uint64_t code_words = n / 16 + 2 * POS_PAD_WORDS + 512;

@@ -17,6 +17,10 @@
 //   FASTKMER_CLI_SPECTRUM=<n>  writes <outputDir>/spectrum.txt, "<c>\t<distinct k-mers>\n" for the
 //       nonzero entries of the n-entry abundance spectrum, ascending; the last entry (count >= n - 1)
 //       as ">=<n - 1>\t..."; written whether or not write is set
+//   FASTKMER_CLI_FORMAT=fasta|fastq|auto  the input's format (default fasta; auto: FASTQ iff the
+//       file's first byte is '@'); any other value is a usage error
+//   FASTKMER_CLI_MIN_QUAL=<q> / FASTKMER_CLI_QUAL_OFFSET=33|64  FASTQ only: bases with a Phred score
+//       below q count as N (default 0: qualities ignored) / the quality encoding (default 33)
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -105,6 +109,23 @@ int main(int argc, char **argv) {
         return 1;
     }
     const bool ranged = has_min || has_max;
+    const char *fmt_env = getenv("FASTKMER_CLI_FORMAT");
+    int format = FK_FORMAT_FASTA;  // -1: auto
+    if (fmt_env && fmt_env[0]) {
+        if (!strcmp(fmt_env, "fastq"))
+            format = FK_FORMAT_FASTQ;
+        else if (!strcmp(fmt_env, "auto"))
+            format = -1;
+        else if (strcmp(fmt_env, "fasta")) {
+            fprintf(stderr, "FASTKMER_CLI_FORMAT=%s: expected fasta, fastq or auto\n", fmt_env);
+            return usage(argv[0]);
+        }
+    }
+    bool has_minq, has_qoff;
+    uint64_t min_qual = 0, qual_off = 33;
+    if (!env_u64("FASTKMER_CLI_MIN_QUAL", 0, 93, &has_minq, &min_qual) ||
+        !env_u64("FASTKMER_CLI_QUAL_OFFSET", 33, 64, &has_qoff, &qual_off))
+        return 1;
     char outdir[4096];
     fk_output_dir(&cfg, output, prefix, outdir, sizeof(outdir));
     // TestConfiguration.toString (test/package.scala:37-39)
@@ -146,6 +167,14 @@ int main(int argc, char **argv) {
     fk_ctx *ctx = nullptr;
     if (fk_create(&cfg, &ctx) != FK_OK) {
         fprintf(stderr, "fk_create: %s\n", fk_last_error());
+        if (map) munmap((void *)map, size);
+        close(fd);
+        return 1;
+    }
+    if (format < 0) format = size && map[0] == '@' ? FK_FORMAT_FASTQ : FK_FORMAT_FASTA;
+    if (format != FK_FORMAT_FASTA && fk_set_input_format(ctx, format, (int32_t)min_qual, (int32_t)qual_off) != FK_OK) {
+        fprintf(stderr, "invalid configuration: %s\n", fk_last_error());
+        fk_destroy(ctx);
         if (map) munmap((void *)map, size);
         close(fd);
         return 1;

@@ -362,6 +362,14 @@ hipError_t launch_hold_stream(const uint32_t *flag, uint64_t max_ticks, hipStrea
 // ---- synthetic input
 hipError_t launch_synth(uint8_t *out, uint64_t nbytes, SynthParams p, hipStream_t s);
 
+// ---- FASTQ input (fk_fastq.inc): the record-aligned range [a, b) of buf (b - a < 2^32) normalised in
+// place to text the FASTA parsers read as the same reads; src != nullptr: copied from src[a, b) first.
+// final_: the input ends at b.  info[0..4): records, masked bases, ~(first malformed record) or 0, index
+// overflow.  ws: fastq_ws_bytes(b - a) bytes.
+uint64_t fastq_ws_bytes(uint64_t range);
+hipError_t launch_fastq_normalise(uint8_t *buf, const uint8_t *src, uint64_t a, uint64_t b, int final_, int min_q,
+                                  int q_off, void *ws, unsigned long long *info, hipStream_t s);
+
 // ---- bin-file text (fk_format.inc) and a small gather: out[i] = src[idx[i]]
 hipError_t launch_format_lens(const uint32_t *counts, uint64_t n, int k, const uint64_t *bin_off, uint32_t nlb,
                               int eof, uint32_t *len, hipStream_t s);

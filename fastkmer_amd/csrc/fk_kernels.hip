@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <limits>
 #include <type_traits>
 
@@ -331,6 +332,7 @@ hipError_t scan_excl_max_i64(const int64_t *in, int64_t *out, uint64_t n, ScanWo
 }
 
 #include "fk_parse.inc"
+#include "fk_fastq.inc"
 #include "fk_signature.inc"
 #include "fk_map_fused.inc"
 #include "fk_records.inc"

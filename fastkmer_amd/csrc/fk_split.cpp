@@ -1,4 +1,5 @@
-// fk_split.cpp -- a rank's input split of a FASTA file (host code, no GPU).
+// fk_split.cpp -- a rank's input split of a FASTA file, or of a FASTQ file (plan_split_fastq, at the
+// end), as host code with no GPU.
 //
 // Replaces the FASTdoop input splits the reference hands its map tasks
 // (SparkBinKmerCounter.scala:993, 1009-1012): the file is cut into byte ranges
@@ -236,6 +237,52 @@ int plan_split(int fd, uint64_t n, int world, int rank, int k, int sequence_type
     plan.segs.push_back(SplitSeg{true, "\n", 0, 1});
     plan.total = 0;
     for (const SplitSeg &s : plan.segs) plan.total += s.len;
+    return 0;
+}
+
+// First FASTQ record start at or after p (p == 0: 0), n if none: the first line start L >= p with
+// '@' at L and '+' at the start of the line two after it.  Reads forward in windows that double until
+// the window holds the answer or reaches the end of the file.
+static bool fastq_record_start(Reader &rd, uint64_t p, uint64_t *out) {
+    if (p == 0) {
+        *out = 0;
+        return true;
+    }
+    for (uint64_t w = 1ull << 16;; w *= 2) {
+        if (!rd.read(p - 1, w + 1)) return false;
+        const std::vector<uint8_t> &b = rd.buf;  // b[j] is byte p - 1 + j
+        const bool whole = p - 1 + b.size() >= rd.n;
+        std::vector<size_t> ls;  // line starts at or after p, as indices of b
+        for (size_t j = 0; j + 1 < b.size(); ++j)
+            if (b[j] == '\n') ls.push_back(j + 1);
+        for (size_t i = 0; i + 2 < ls.size(); ++i)
+            if (b[ls[i]] == '@' && b[ls[i + 2]] == '+') {
+                *out = p - 1 + ls[i];
+                return true;
+            }
+        if (whole) break;
+    }
+    *out = rd.n;
+    return true;
+}
+
+int plan_split_fastq(int fd, uint64_t n, int world, int rank, SplitPlan &plan, std::string &err) {
+    plan = SplitPlan{};
+    if (world < 1 || rank < 0 || rank >= world) {
+        err = "bad rank " + std::to_string(rank) + " of " + std::to_string(world);
+        return -1;
+    }
+    Reader rd{fd, n, {}, {}};
+    const uint64_t r0 = (uint64_t)((unsigned __int128)n * (uint64_t)rank / (uint64_t)world);
+    const uint64_t r1 = (uint64_t)((unsigned __int128)n * (uint64_t)(rank + 1) / (uint64_t)world);
+    uint64_t lo = 0, hi = n;
+    if (!fastq_record_start(rd, r0, &lo) || (rank + 1 < world && !fastq_record_start(rd, r1, &hi))) {
+        err = rd.err;
+        return -1;
+    }
+    if (hi > lo) plan.segs.push_back(SplitSeg{false, {}, lo, hi - lo});
+    plan.total = hi > lo ? hi - lo : 0;
+    plan.lo = lo, plan.hi = hi;
     return 0;
 }
 

@@ -168,6 +168,63 @@ int fk_ingest_device(fk_ctx *ctx, const void *d_fasta, size_t n, int last);
 int fk_split_bytes(const char *path, int32_t world, int32_t rank, int32_t k, int32_t sequence_type, uint8_t *out,
                    size_t cap, size_t *n);
 int fk_ingest_file_range(fk_ctx *ctx, const char *path, int32_t world, int32_t rank, uint64_t window_bytes);
+/* ---- FASTQ input (the reference marks the gap: its FASTQInputFileFormat lines
+ * are commented out, SBKC:975, 1007) ----
+ * Strict four-line records: "@name", sequence, "+[anything]", quality; one line
+ * each (no wrapped sequences), LF or CRLF, the final newline may be missing,
+ * blank lines may trail the input, reads may be empty, quality lines may begin
+ * with or contain '@', '+' or '>'.  Sequence bytes follow the FASTA rules: only
+ * ACGT are valid; N, lowercase, IUPAC codes and '\r' are invalid positions.  A
+ * record starts at a line beginning with '@' whose second-next line begins with
+ * '+' (exact for this grammar).
+ * A small device stage in front of the FASTA parse rewrites the device input in
+ * place, at the same byte offsets: the '@', the '+' and the first byte of a
+ * non-empty quality line become '>' (the '+' and quality lines are header lines
+ * to the parser), and with min_quality > 0 every base whose Phred score
+ * (quality byte - quality_offset) is below it becomes 'N'.  fk_stats.kmers,
+ * distinct and every result call then equal those of the equivalent FASTA job
+ * ('@' -> '>', the '+' and quality lines dropped, masked bases as 'N');
+ * fk_stats.fasta_bytes is the FASTQ bytes ingested, and fk_stats.positions
+ * counts the sequence bytes plus one separator per header line the parser sees:
+ * three per record (two for a record with an empty quality line).
+ * The format applies to fk_ingest (one call or chunks, pinned or pageable),
+ * fk_ingest_device (the borrowed buffer is left as it is: the stage copies it
+ * into the context's own input; less than 4 GiB per call), fk_ingest_file_range
+ * (the FASTQ split), fk_balance_bins (a sample of whole FASTQ records),
+ * fk_signature_counts and jobs with a communicator.  fk_balance_bins_file
+ * returns FK_E_INVALID on a FASTQ context.
+ * Malformed input -- a record without its '@' or its '+', a quality line whose
+ * length differs from the sequence's, an input ending inside a record -- makes
+ * the job's fk_map / fk_finish return FK_E_INVALID, the message naming the
+ * first malformed record (0-based); the context takes a new job afterwards.
+ * An input with more than one line per 4 bytes over a stretch of it (reads of
+ * under 5 bases throughout) is refused the same way. */
+#define FK_FORMAT_FASTA 0
+#define FK_FORMAT_FASTQ 1
+/* Between jobs only (FK_E_STATE after a job's first fk_ingest and before its
+ * fk_finish / fk_map).  FASTQ needs sequence_type == 0 (else FK_E_INVALID).
+ * min_quality: Phred score below which a base counts as N (0: qualities are
+ * ignored; at most 93); quality_offset: 33 or 64.  (FASTA, 0, 33) is the
+ * default and is exactly the FASTA-only behaviour, with no extra launch. */
+int fk_set_input_format(fk_ctx *ctx, int32_t format, int32_t min_quality, int32_t quality_offset);
+int fk_input_format(const fk_ctx *ctx, int32_t *format, int32_t *min_quality, int32_t *quality_offset);
+/* After fk_finish / fk_map of a FASTQ job (also one that failed on a malformed
+ * record): out[0] = records, out[1] = bases whose quality is below min_quality
+ * (whatever the base), out[2] = index of the first malformed record
+ * (UINT64_MAX: none).  FK_E_STATE before the first such job. */
+int fk_fastq_info(fk_ctx *ctx, uint64_t out[3]);
+/* Host only.  The offset of the start of the last record whose '@' line and
+ * '+' line both begin inside buf[0, n): the last line start L with
+ * buf[L] == '@' such that the line two after L exists and begins with '+'
+ * (buf[0] counts as a line start).  *off = n when there is none.  A streamed
+ * fk_ingest maps only below this frontier: the record it names may be
+ * incomplete. */
+int fk_fastq_frontier(const uint8_t *buf, size_t n, size_t *off);
+/* Host only: fk_split_bytes for a FASTQ file (sequence_type 0 semantics: the
+ * whole records whose '@' line starts in the rank's byte range; rank 0 also
+ * gets what precedes the first record start). */
+int fk_split_bytes_fastq(const char *path, int32_t world, int32_t rank, uint8_t *out, size_t cap, size_t *n);
+
 /* Fill a caller's device buffer (current device) with the same bytes as
  * fk_synth_fasta_host (benchmarks: the input is staged to pinned host memory). */
 int fk_synth_fasta_to_device(void *d_out, uint64_t first_read, uint64_t n_reads, int32_t read_len,
@@ -403,6 +460,11 @@ int fk_debug_fingerprint_bits(int32_t device, int32_t bits);
  * its launches since the last reset (out[0..16)); only a library built with
  * -DFK_PROBES records them (FK_E_STATE otherwise). */
 int fk_debug_map_cycles(uint64_t *out16, int32_t reset);
+
+/* Measurement hook: after the fk_map / fk_finish of a FASTQ job, *ms = the device-event time summed
+ * over the job's normalise launches (each the stage's two kernels and the memset before them),
+ * *launches = how many there were. */
+int fk_debug_fastq_ms(fk_ctx *ctx, double *ms, uint64_t *launches);
 
 /* ---- bin-signature diagnostics (executeFindBinSignaturesJob, SBKC:956-986) ----
  * fk_signature_counts: after the final fk_ingest (the input is left in place,
