@@ -62,6 +62,17 @@ class fk_stats(ctypes.Structure):
                                        ("split_buckets", ctypes.c_uint64),
                                        ("sub_buckets", ctypes.c_uint64)]
 
+
+class fk_read_stat(ctypes.Structure):
+    """Mirror of fk_read_stat (include/fastkmer.h): one read's statistics, 32 bytes."""
+    _fields_ = [(n, ctypes.c_uint32) for n in ("windows", "hits", "min", "median", "max", "reserved")] + \
+               [("sum", ctypes.c_uint64)]
+
+
+READ_STAT_DTYPE = np.dtype([(n, np.uint32) for n in ("windows", "hits", "min", "median", "max", "reserved")] +
+                           [("sum", np.uint64)])  # the numpy view of fk_read_stat
+READ_TILE = 4096  # FK_READ_TILE: positions per workgroup tile of the window kernel
+
 COMM_ID_BYTES = 128
 MAX_COUNT = 0xFFFFFFFF  # max_count of the count-range calls: no upper bound
 
@@ -148,6 +159,14 @@ def lib():
         "fk_query": (ctypes.c_int, [P, P, SZ, P, P]),
         "fk_query_device": (ctypes.c_int, [P, P, SZ, P, P]),
         "fk_query_sequence": (ctypes.c_int, [P, ctypes.c_char_p, SZ, P, SZ, ctypes.POINTER(SZ)]),
+        "fk_reads_csr": (ctypes.c_int, [ctypes.c_char_p, SZ, I32, I32, I32, P, SZ, P, SZ, ctypes.POINTER(SZ),
+                                        ctypes.POINTER(SZ)]),
+        "fk_read_counts_device": (ctypes.c_int, [P, P, P, SZ, P, P]),
+        "fk_read_counts": (ctypes.c_int, [P, P, P, SZ, P, P]),
+        "fk_read_stats_of_counts_device": (ctypes.c_int, [P, P, P, P, SZ, ctypes.c_uint32, ctypes.c_uint32, P]),
+        "fk_read_stats_device": (ctypes.c_int, [P, P, P, SZ, ctypes.c_uint32, ctypes.c_uint32, P, SZ, P]),
+        "fk_read_stats": (ctypes.c_int, [P, P, P, SZ, ctypes.c_uint32, ctypes.c_uint32, P]),
+        "fk_read_stats_scratch_bytes": (SZ, [SZ]),
         "fk_spectrum": (ctypes.c_int, [P, P, SZ, P]),
         "fk_spectrum_device": (ctypes.c_int, [P, P, SZ, P]),
         "fk_bin_sizes_range": (ctypes.c_int, [P, ctypes.c_uint32, ctypes.c_uint32, P]),
@@ -272,6 +291,52 @@ def fastq_frontier(buf: bytes) -> int:
     off = ctypes.c_size_t()
     _check(lib().fk_fastq_frontier(raw, len(raw), ctypes.byref(off)))
     return off.value
+
+
+def reads_csr(text, input_format: str = "fasta", min_quality: int = 0, quality_offset: int = 33):
+    """fk_reads_csr: FASTA / FASTQ text cut into a CSR read batch as the count sees it -- (bases, offsets):
+    uint8[n_bases] sequence bytes back to back, uint64[n_reads + 1] ascending from 0 to n_bases.  Host only.
+    FastKmerError (FK_E_INVALID) naming the first malformed FASTQ record."""
+    if input_format not in FORMATS:
+        raise ValueError(f"input_format must be one of {sorted(FORMATS)}")
+    raw = text.encode() if isinstance(text, str) else bytes(text)
+    L = lib()
+    nr, nb = ctypes.c_size_t(), ctypes.c_size_t()
+    args = (raw, len(raw), FORMATS[input_format], int(min_quality), int(quality_offset))
+    _check(L.fk_reads_csr(*args, None, 0, None, 0, ctypes.byref(nr), ctypes.byref(nb)))
+    bases = np.zeros(nb.value, dtype=np.uint8)
+    offsets = np.zeros(nr.value + 1, dtype=np.uint64)
+    _check(L.fk_reads_csr(*args, bases.ctypes.data, bases.size, offsets.ctypes.data, nr.value, ctypes.byref(nr),
+                          ctypes.byref(nb)))
+    return bases, offsets
+
+
+def read_stats_scratch_bytes(n_bases: int) -> int:
+    """fk_read_stats_scratch_bytes: the scratch read_stats_ptr needs for a batch of n_bases bases."""
+    return lib().fk_read_stats_scratch_bytes(int(n_bases))
+
+
+def filter_reads(stats, min_hits: int = 0, max_hits: int | None = None) -> np.ndarray:
+    """kmc_tools filter on read statistics: the bool mask of the reads whose number of k-mers with a count
+    in the range the statistics were made with (stats["hits"]) lies in [min_hits, max_hits], both ends
+    inclusive (max_hits None: no upper bound)."""
+    hits = np.asarray(stats)["hits"]
+    keep = hits >= min_hits
+    if max_hits is not None:
+        keep &= hits <= max_hits
+    return keep
+
+
+def _csr_arrays(bases, offsets):
+    if isinstance(bases, (bytes, bytearray, str)):
+        bases = np.frombuffer(bases.encode() if isinstance(bases, str) else bytes(bases), dtype=np.uint8)
+    b = np.ascontiguousarray(bases, dtype=np.uint8).reshape(-1)
+    o = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+    if o.size < 1:
+        raise ValueError("offsets has n_reads + 1 entries")
+    if int(o[-1]) != b.size:
+        raise ValueError(f"offsets ends at {int(o[-1])}, bases holds {b.size}")
+    return b, o
 
 
 def decode_keys(keys: np.ndarray, k: int) -> list[str]:
@@ -651,6 +716,60 @@ class KmerCounter:
         _check(lib().fk_query_sequence(self._h, raw, len(raw), counts.ctypes.data if nwin else None, nwin,
                                        ctypes.byref(n)))
         return counts[:n.value]
+
+    # -- per-read abundance profiles (fk_read_counts*, fk_read_stats*)
+    def read_counts(self, bases, offsets, return_valid: bool = False):
+        """The count of every window bases[p, p + k) of a CSR read batch (reads_csr), indexed by base
+        position: a uint32 array of n_bases entries, 0 where no valid window starts (it would cross a read
+        end or hold a byte other than A/C/G/T), for an absent k-mer or a bin another rank owns.  With
+        return_valid also the uint8 array that is 1 exactly at the valid windows."""
+        b, o = _csr_arrays(bases, offsets)
+        counts = np.zeros(b.size, dtype=np.uint32)
+        valid = np.zeros(b.size, dtype=np.uint8) if return_valid else None
+        _check(lib().fk_read_counts(self._h, b.ctypes.data, o.ctypes.data, o.size - 1, counts.ctypes.data,
+                                    valid.ctypes.data if return_valid else None))
+        return (counts, valid) if return_valid else counts
+
+    def read_stats(self, bases_or_text, offsets=None, min_count: int = 1, max_count: int | None = None,
+                   input_format: str = "fasta", min_quality: int = 0, quality_offset: int = 33) -> np.ndarray:
+        """Per-read statistics (a structured array mirroring fk_read_stat: windows, hits, min, median, max,
+        reserved, sum) of a CSR batch (bases, offsets), or with offsets None of FASTA / FASTQ text cut by
+        reads_csr.  hits counts the valid windows with min_count <= count <= max_count."""
+        if offsets is None:
+            bases_or_text, offsets = reads_csr(bases_or_text, input_format, min_quality, quality_offset)
+        b, o = _csr_arrays(bases_or_text, offsets)
+        hi = MAX_COUNT if max_count is None else int(max_count)
+        if not (0 <= int(min_count) <= MAX_COUNT and 0 <= hi <= MAX_COUNT):
+            raise ValueError("min_count / max_count are 32-bit counts")
+        stats = np.zeros(o.size - 1, dtype=READ_STAT_DTYPE)
+        _check(lib().fk_read_stats(self._h, b.ctypes.data, o.ctypes.data, o.size - 1, int(min_count), hi,
+                                   stats.ctypes.data))
+        return stats
+
+    def read_counts_ptr(self, d_bases: int, d_offsets: int, n_reads: int, d_counts: int, d_valid: int = 0) -> None:
+        """fk_read_counts_device: device pointers (uint8 bases, uint64 offsets[n_reads + 1], uint32
+        counts[n_bases], uint8 valid[n_bases] if given), queued on the context's stream (set_stream);
+        nothing is allocated or synchronised."""
+        _check(lib().fk_read_counts_device(self._h, ctypes.c_void_p(d_bases), ctypes.c_void_p(d_offsets), n_reads,
+                                           ctypes.c_void_p(d_counts), ctypes.c_void_p(d_valid) if d_valid else None))
+
+    def read_stats_ptr(self, d_bases: int, d_offsets: int, n_reads: int, d_scratch: int, scratch_bytes: int,
+                       d_stats: int, min_count: int = 1, max_count: int | None = None) -> None:
+        """fk_read_stats_device: the window counts then the per-read reduction through the caller's
+        scratch (read_stats_scratch_bytes(n_bases) bytes) into fk_read_stat[n_reads] at d_stats."""
+        _check(lib().fk_read_stats_device(self._h, ctypes.c_void_p(d_bases), ctypes.c_void_p(d_offsets), n_reads,
+                                          int(min_count), MAX_COUNT if max_count is None else int(max_count),
+                                          ctypes.c_void_p(d_scratch), scratch_bytes, ctypes.c_void_p(d_stats)))
+
+    def read_stats_of_counts_ptr(self, d_counts: int, d_valid: int, d_offsets: int, n_reads: int, d_stats: int,
+                                 min_count: int = 1, max_count: int | None = None) -> None:
+        """fk_read_stats_of_counts_device: per-read statistics of position-indexed device arrays (one
+        rank's counts, or the ranks' summed); d_valid 0: every existing window is valid."""
+        _check(lib().fk_read_stats_of_counts_device(self._h, ctypes.c_void_p(d_counts),
+                                                    ctypes.c_void_p(d_valid) if d_valid else None,
+                                                    ctypes.c_void_p(d_offsets), n_reads, int(min_count),
+                                                    MAX_COUNT if max_count is None else int(max_count),
+                                                    ctypes.c_void_p(d_stats)))
 
     def bin_dict(self, b: int, min_count: int = 1, max_count: int | None = None) -> dict:
         keys, counts = self.get_bin(b, min_count, max_count)

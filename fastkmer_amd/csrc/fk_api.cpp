@@ -389,6 +389,8 @@ struct fk_ctx {
     DevBuf gather_keys, gather_counts;    // fk_get_bin's gather of one bin
     // fk_query / fk_query_sequence: staging of one chunk's keys (or bases), counts and bins
     DevBuf q_in, q_counts, q_bins;
+    // fk_read_counts / fk_read_stats: one chunk's offsets, valid flags and statistics (bases in q_in, counts in q_counts)
+    DevBuf rd_off, rd_valid, rd_stats;
     // fk_spectrum: the histogram and its tail sum; fk_get_bin_range: kept k-mers per bucket of one bin
     // and their scan (the filtered bin itself goes through gather_keys / gather_counts)
     DevBuf sp_hist, rg_kept, rg_off;
@@ -725,7 +727,7 @@ FK_EXPORT void fk_destroy(fk_ctx *c) {
                       &c->cell_total, &c->cell_base, &c->flags, &c->flag_scan, &c->buckets, &c->keys,
                       &c->out_keys, &c->out_counts, &c->bucket_unique, &c->dense_off, &c->dense_keys,
                       &c->dense_counts, &c->bin_off, &c->misc, &c->tier_list, &c->mid, &c->sc_total, &c->gather_keys, &c->gather_counts,
-                      &c->q_in, &c->q_counts, &c->q_bins, &c->sp_hist, &c->rg_kept, &c->rg_off,
+                      &c->q_in, &c->q_counts, &c->q_bins, &c->rd_off, &c->rd_valid, &c->rd_stats, &c->sp_hist, &c->rg_kept, &c->rg_off,
                       &c->sp_base, &c->sp_keys, &c->sp_subs, &c->sp_par, &c->sp_fb, &c->mid_fb};
     for (DevBuf *b : bufs) release(*b);
     release(c->fq_ws);
@@ -3926,6 +3928,279 @@ FK_EXPORT int fk_write_bins_range(fk_ctx *c, const char *out_dir, uint32_t min_c
                                  max_count, fkeys.as<uint64_t>(), fcounts.as<uint32_t>(), c->stream));
     // the writer ends with the stream drained (its text copy), before the temporaries are released
     return write_bin_text(c, out_dir, fkeys.as<uint64_t>(), fcounts.as<uint32_t>(), D, d_off.as<uint64_t>(), h_off);
+}
+
+// ---------------------------------------------------------------------------
+// per-read abundance profiles of the counted result (fk_reads.inc)
+// ---------------------------------------------------------------------------
+
+static_assert(FK_READ_TILE == READ_TILE, "fastkmer.h names the kernel's tile");
+static_assert(sizeof(fk_read_stat) == 32 && sizeof(ReadStat) == 32, "fk_read_stat is 32 bytes");
+
+// Host only: FASTA / FASTQ text cut into a CSR read batch, the reads as the count sees them.
+namespace {
+struct CsrOut {
+    uint8_t *bases;
+    size_t cap_bases;
+    uint64_t *offsets;
+    size_t cap_reads;
+    size_t nr = 0, nb = 0;
+    bool fill, over = false;
+    void begin_read() {
+        if (fill) {
+            if (nr < cap_reads)
+                offsets[nr] = nb;
+            else
+                over = true;
+        }
+        ++nr;
+    }
+    void append(const uint8_t *p, size_t len) {
+        if (fill) {
+            if (nb + len <= cap_bases)
+                memcpy(bases + nb, p, len);
+            else
+                over = true;
+        }
+        nb += len;
+    }
+};
+}  // namespace
+
+FK_EXPORT int fk_reads_csr(const uint8_t *text, size_t n, int32_t format, int32_t min_quality, int32_t quality_offset,
+                           uint8_t *bases, size_t cap_bases, uint64_t *offsets, size_t cap_reads, size_t *n_reads,
+                           size_t *n_bases) {
+    if ((!text && n) || !n_reads || !n_bases) return set_err(FK_E_INVALID, "null argument");
+    *n_reads = 0;
+    *n_bases = 0;
+    if (format != FK_FORMAT_FASTA && format != FK_FORMAT_FASTQ) return set_err(FK_E_INVALID, "unknown input format %d", format);
+    if (quality_offset != 33 && quality_offset != 64)
+        return set_err(FK_E_INVALID, "quality_offset must be 33 or 64, got %d", quality_offset);
+    if (min_quality < 0 || min_quality > 93) return set_err(FK_E_INVALID, "min_quality must be in 0..93, got %d", min_quality);
+    CsrOut o{bases, cap_bases, offsets, cap_reads};
+    o.fill = bases && offsets;
+    uint64_t bad = UINT64_MAX;
+    if (format == FK_FORMAT_FASTA) {
+        // the parse's grammar (fk_parse.inc, oracle for_each_read): a non-empty line beginning with '>' is a
+        // header, the lines up to the next header are its read without their '\n', lines before the first
+        // header are no sequence
+        bool in_record = false;
+        for (size_t pos = 0; pos < n;) {
+            const uint8_t *nl = static_cast<const uint8_t *>(memchr(text + pos, '\n', n - pos));
+            const size_t e = nl ? (size_t)(nl - text) : n;
+            if (e > pos && text[pos] == '>') {
+                in_record = true;
+                o.begin_read();
+            } else if (in_record) {
+                o.append(text + pos, e - pos);
+            }
+            pos = e + 1;
+        }
+    } else {
+        // fk_fastq.inc's grammar: the lines up to the last one holding a byte other than '\n' / '\r', rounded
+        // up to whole records of four where blank lines follow; a trailing '\r' is outside the two lengths
+        std::vector<size_t> ls;  // line starts, then n + 1 (every line ends one before the next start)
+        for (size_t pos = 0; pos < n;) {
+            ls.push_back(pos);
+            const uint8_t *nl = static_cast<const uint8_t *>(memchr(text + pos, '\n', n - pos));
+            pos = nl ? (size_t)(nl - text) + 1 : n + 1;
+        }
+        const size_t nlines = ls.size();
+        ls.push_back(n && text[n - 1] == '\n' ? n : n + 1);
+        size_t ntext = 0;  // lines up to the last one with text
+        for (size_t i = nlines; i-- > 0 && !ntext;)
+            for (size_t q = ls[i]; q + 1 < ls[i + 1]; ++q)
+                if (text[q] != '\r') {
+                    ntext = i + 1;
+                    break;
+                }
+        const size_t neff = std::min(nlines, (ntext + 3) & ~(size_t)3), nrec = neff / 4;
+        if (neff & 3) bad = nrec;
+        for (size_t r = 0; r < nrec && r < bad; ++r) {
+            const size_t s0 = ls[4 * r], e0 = ls[4 * r + 1] - 1, s1 = ls[4 * r + 1], e1 = ls[4 * r + 2] - 1;
+            const size_t s2 = ls[4 * r + 2], e2 = ls[4 * r + 3] - 1, s3 = ls[4 * r + 3], e3 = std::min(ls[4 * r + 4] - 1, n);
+            size_t len1 = e1 - s1, len3 = e3 - s3;
+            if (len1 && text[e1 - 1] == '\r') --len1;
+            if (len3 && text[e3 - 1] == '\r') --len3;
+            if (!(e0 > s0 && text[s0] == '@' && e2 > s2 && text[s2] == '+' && len1 == len3)) {
+                bad = r;
+                break;
+            }
+            o.begin_read();
+            const size_t at = o.nb;
+            o.append(text + s1, e1 - s1);
+            if (o.fill && !o.over && min_quality > 0)
+                for (size_t j = 0; j < len1; ++j)
+                    if ((int)text[s3 + j] - quality_offset < min_quality) bases[at + j] = 'N';
+        }
+    }
+    if (o.fill) {
+        if (o.nr <= cap_reads)
+            offsets[o.nr] = o.nb;
+        else
+            o.over = true;
+    }
+    *n_reads = o.nr;
+    *n_bases = o.nb;
+    if (bad != UINT64_MAX)
+        return set_err(FK_E_INVALID, "FASTQ record %llu is malformed (no '@' or '+' line, quality and sequence of "
+                                     "different lengths, or the input ends inside it)", (unsigned long long)bad);
+    if (o.over)
+        return set_err(FK_E_RANGE, "the text holds %zu reads of %zu bases, the buffers hold %zu and %zu", o.nr, o.nb,
+                       cap_reads, cap_bases);
+    return FK_OK;
+}
+
+FK_EXPORT size_t fk_read_stats_scratch_bytes(size_t n_bases) { return 5 * n_bases; }
+
+// offsets[0] == 0 and ascending (host forms)
+static int check_offsets(const uint64_t *offsets, size_t n_reads) {
+    if (offsets[0] != 0) return set_err(FK_E_INVALID, "offsets[0] is %llu, not 0", (unsigned long long)offsets[0]);
+    for (size_t i = 0; i < n_reads; ++i)
+        if (offsets[i + 1] < offsets[i])
+            return set_err(FK_E_INVALID, "offsets do not ascend at read %zu (%llu after %llu)", i,
+                           (unsigned long long)offsets[i + 1], (unsigned long long)offsets[i]);
+    return FK_OK;
+}
+
+static int need_all_counts(const fk_ctx *c, const char *what) {
+    if (c->cfg.n_ranks > 1)
+        return set_err(FK_E_INVALID, "%s needs every k-mer's count and this context is rank %d of %d: sum the ranks' "
+                                     "fk_read_counts arrays and reduce them with fk_read_stats_of_counts_device",
+                       what, c->cfg.rank, c->cfg.n_ranks);
+    return FK_OK;
+}
+
+FK_EXPORT int fk_read_counts_device(fk_ctx *c, const void *d_bases, const void *d_offsets, size_t n_reads,
+                                    void *d_counts, void *d_valid) {
+    if (!c) return set_err(FK_E_INVALID, "null ctx");
+    DeviceGuard dg_(c->device);
+    QueryTables t;
+    FK_TRY(query_tables(c, t));
+    if (n_reads == 0) return FK_OK;
+    if (!d_bases || !d_offsets || !d_counts) return set_err(FK_E_INVALID, "null argument");
+    HIP_TRY(launch_read_counts(c->KW, t, static_cast<const uint8_t *>(d_bases), static_cast<const uint64_t *>(d_offsets),
+                               n_reads, 0, UINT64_MAX, static_cast<uint32_t *>(d_counts),
+                               static_cast<uint8_t *>(d_valid), c->stream));
+    return FK_OK;
+}
+
+FK_EXPORT int fk_read_counts(fk_ctx *c, const uint8_t *bases, const uint64_t *offsets, size_t n_reads,
+                             uint32_t *counts, uint8_t *valid) {
+    if (!c) return set_err(FK_E_INVALID, "null ctx");
+    DeviceGuard dg_(c->device);
+    QueryTables t;
+    FK_TRY(query_tables(c, t));
+    if (!offsets) return set_err(FK_E_INVALID, "null argument");
+    FK_TRY(check_offsets(offsets, n_reads));
+    const size_t n = (size_t)offsets[n_reads], k = (size_t)c->cfg.k;
+    if (n == 0) return FK_OK;
+    if (!bases || !counts) return set_err(FK_E_INVALID, "null argument");
+    hipStream_t s = c->stream;
+    // positions [at, at + nc) read the bases [at, at + nc + k - 1) and the offsets of the reads that touch them,
+    // rebased: the first read cut at `at`, the last at the end of the halo
+    const size_t chunk = (size_t)std::min<uint64_t>(query_chunk(), n);
+    FK_TRY(ensure(c->q_in, chunk + k));
+    FK_TRY(ensure(c->q_counts, (chunk + k) * 4));
+    if (valid) FK_TRY(ensure(c->rd_valid, chunk + k));
+    std::vector<uint64_t> sub;
+    const uint64_t *const oend = offsets + n_reads + 1;
+    for (size_t at = 0; at < n; at += chunk) {
+        const size_t nc = std::min(chunk, n - at), len = std::min(nc + k - 1, n - at);
+        const uint64_t *i0 = std::upper_bound(offsets, oend, (uint64_t)at) - 1;  // the last read beginning at or before
+        const uint64_t *i1 = std::lower_bound(i0 + 1, oend, (uint64_t)(at + len));
+        const size_t nsub = (size_t)(i1 - i0);
+        sub.assign(nsub + 1, 0);
+        for (size_t j = 1; j < nsub; ++j) sub[j] = i0[j] - at;
+        sub[nsub] = len;
+        FK_TRY(ensure(c->rd_off, (nsub + 1) * 8));
+        HIP_TRY(hipMemcpyAsync(c->q_in.p, bases + at, len, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(c->rd_off.p, sub.data(), (nsub + 1) * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(launch_read_counts(c->KW, t, c->q_in.as<uint8_t>(), c->rd_off.as<uint64_t>(), nsub, len, len,
+                                   c->q_counts.as<uint32_t>(), valid ? c->rd_valid.as<uint8_t>() : nullptr, s));
+        HIP_TRY(hipMemcpyAsync(counts + at, c->q_counts.p, nc * 4, hipMemcpyDeviceToHost, s));
+        if (valid) HIP_TRY(hipMemcpyAsync(valid + at, c->rd_valid.p, nc, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));  // the staging buffers are free for the next chunk
+    }
+    return FK_OK;
+}
+
+FK_EXPORT int fk_read_stats_of_counts_device(fk_ctx *c, const void *d_counts, const void *d_valid, const void *d_offsets,
+                                             size_t n_reads, uint32_t min_count, uint32_t max_count, void *d_stats) {
+    if (!c) return set_err(FK_E_INVALID, "null ctx");
+    DeviceGuard dg_(c->device);
+    FK_TRY(check_count_range(min_count, max_count));
+    if (n_reads == 0) return FK_OK;
+    if (!d_counts || !d_offsets || !d_stats) return set_err(FK_E_INVALID, "null argument");
+    HIP_TRY(launch_read_stats(static_cast<const uint32_t *>(d_counts), static_cast<const uint8_t *>(d_valid),
+                              static_cast<const uint64_t *>(d_offsets), n_reads, UINT64_MAX, c->cfg.k, min_count,
+                              max_count, static_cast<ReadStat *>(d_stats), c->stream));
+    return FK_OK;
+}
+
+FK_EXPORT int fk_read_stats_device(fk_ctx *c, const void *d_bases, const void *d_offsets, size_t n_reads,
+                                   uint32_t min_count, uint32_t max_count, void *d_scratch, size_t scratch_bytes,
+                                   void *d_stats) {
+    if (!c) return set_err(FK_E_INVALID, "null ctx");
+    DeviceGuard dg_(c->device);
+    FK_TRY(need_all_counts(c, "fk_read_stats_device"));
+    QueryTables t;
+    FK_TRY(query_tables(c, t));
+    FK_TRY(check_count_range(min_count, max_count));
+    if (n_reads == 0) return FK_OK;
+    if (!d_bases || !d_offsets || !d_stats || (!d_scratch && scratch_bytes)) return set_err(FK_E_INVALID, "null argument");
+    if (reinterpret_cast<uintptr_t>(d_scratch) & 3) return set_err(FK_E_INVALID, "d_scratch must be 4-byte aligned");
+    // the scratch holds uint32 counts then uint8 valid flags of `cap` positions; the kernels stop at cap
+    const uint64_t cap = scratch_bytes / 5;
+    uint32_t *cnt = static_cast<uint32_t *>(d_scratch);
+    uint8_t *val = static_cast<uint8_t *>(d_scratch) + 4 * cap;
+    if (cap)
+        HIP_TRY(launch_read_counts(c->KW, t, static_cast<const uint8_t *>(d_bases),
+                                   static_cast<const uint64_t *>(d_offsets), n_reads, cap, cap, cnt, val, c->stream));
+    HIP_TRY(launch_read_stats(cnt, val, static_cast<const uint64_t *>(d_offsets), n_reads, cap, c->cfg.k, min_count,
+                              max_count, static_cast<ReadStat *>(d_stats), c->stream));
+    return FK_OK;
+}
+
+FK_EXPORT int fk_read_stats(fk_ctx *c, const uint8_t *bases, const uint64_t *offsets, size_t n_reads,
+                            uint32_t min_count, uint32_t max_count, fk_read_stat *stats) {
+    if (!c) return set_err(FK_E_INVALID, "null ctx");
+    DeviceGuard dg_(c->device);
+    FK_TRY(need_all_counts(c, "fk_read_stats"));
+    QueryTables t;
+    FK_TRY(query_tables(c, t));
+    FK_TRY(check_count_range(min_count, max_count));
+    if (!offsets) return set_err(FK_E_INVALID, "null argument");
+    FK_TRY(check_offsets(offsets, n_reads));
+    if (n_reads == 0) return FK_OK;
+    if ((!bases && offsets[n_reads]) || !stats) return set_err(FK_E_INVALID, "null argument");
+    hipStream_t s = c->stream;
+    // whole reads per chunk: as many as fit FASTKMER_QUERY_CHUNK positions (and as many reads), at least one
+    const uint64_t chunk = query_chunk();
+    std::vector<uint64_t> sub;
+    for (size_t r0 = 0; r0 < n_reads;) {
+        size_t r1 = r0 + 1;
+        while (r1 < n_reads && offsets[r1 + 1] - offsets[r0] <= chunk && r1 - r0 < chunk) ++r1;
+        const size_t nr = r1 - r0, len = (size_t)(offsets[r1] - offsets[r0]);
+        sub.resize(nr + 1);
+        for (size_t j = 0; j <= nr; ++j) sub[j] = offsets[r0 + j] - offsets[r0];
+        FK_TRY(ensure(c->q_in, len));
+        FK_TRY(ensure(c->q_counts, len * 4));
+        FK_TRY(ensure(c->rd_valid, len));
+        FK_TRY(ensure(c->rd_off, (nr + 1) * 8));
+        FK_TRY(ensure(c->rd_stats, nr * sizeof(ReadStat)));
+        if (len) HIP_TRY(hipMemcpyAsync(c->q_in.p, bases + offsets[r0], len, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(c->rd_off.p, sub.data(), (nr + 1) * 8, hipMemcpyHostToDevice, s));
+        if (len)
+            HIP_TRY(launch_read_counts(c->KW, t, c->q_in.as<uint8_t>(), c->rd_off.as<uint64_t>(), nr, len, len,
+                                       c->q_counts.as<uint32_t>(), c->rd_valid.as<uint8_t>(), s));
+        HIP_TRY(launch_read_stats(c->q_counts.as<uint32_t>(), c->rd_valid.as<uint8_t>(), c->rd_off.as<uint64_t>(), nr,
+                                  len, c->cfg.k, min_count, max_count, c->rd_stats.as<ReadStat>(), s));
+        HIP_TRY(hipMemcpyAsync(stats + r0, c->rd_stats.p, nr * sizeof(ReadStat), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        r0 = r1;
+    }
+    return FK_OK;
 }
 
 // ---------------------------------------------------------------------------

@@ -21,6 +21,10 @@
 //       file's first byte is '@'); any other value is a usage error
 //   FASTKMER_CLI_MIN_QUAL=<q> / FASTKMER_CLI_QUAL_OFFSET=33|64  FASTQ only: bases with a Phred score
 //       below q count as N (default 0: qualities ignored) / the quality encoding (default 33)
+//   FASTKMER_CLI_READS=<file>  after the count, the reads of <file> (the job's input format and quality
+//       settings) are profiled against the result: <outputDir>/read_stats.tsv, one line per read,
+//       "index\tlength\twindows\thits\tmin\tmedian\tmax\tsum" (fk_read_stats; hits counts the k-mers with
+//       FASTKMER_CLI_MIN_COUNT <= count <= FASTKMER_CLI_MAX_COUNT); needs useHT = 0, else a usage error
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -126,6 +130,12 @@ int main(int argc, char **argv) {
     if (!env_u64("FASTKMER_CLI_MIN_QUAL", 0, 93, &has_minq, &min_qual) ||
         !env_u64("FASTKMER_CLI_QUAL_OFFSET", 33, 64, &has_qoff, &qual_off))
         return 1;
+    const char *reads_path = getenv("FASTKMER_CLI_READS");
+    if (reads_path && !reads_path[0]) reads_path = nullptr;
+    if (reads_path && cfg.use_ht) {
+        fprintf(stderr, "FASTKMER_CLI_READS needs the sorted count (useHT = 0): a useHT = 1 result cannot be looked up\n");
+        return usage(argv[0]);
+    }
     char outdir[4096];
     fk_output_dir(&cfg, output, prefix, outdir, sizeof(outdir));
     // TestConfiguration.toString (test/package.scala:37-39)
@@ -239,6 +249,58 @@ int main(int argc, char **argv) {
             return 1;
         }
         printf("Spectrum written to %s\n", path.c_str());
+    }
+    if (reads_path) {
+        std::vector<uint8_t> text;
+        FILE *in = fopen(reads_path, "rb");
+        bool ok = in != nullptr;
+        if (ok) {
+            uint8_t buf[1 << 16];
+            for (size_t got; (got = fread(buf, 1, sizeof(buf), in)) > 0;) text.insert(text.end(), buf, buf + got);
+            ok = !ferror(in);
+            fclose(in);
+        }
+        if (!ok) {
+            fprintf(stderr, "cannot open %s\n", reads_path);
+            fk_destroy(ctx);
+            return 1;
+        }
+        // the reads file is cut as the job's input was (auto picked the job's format above)
+        size_t n_reads = 0, n_bases = 0;
+        int rrc = fk_reads_csr(text.data(), text.size(), format, (int32_t)min_qual, (int32_t)qual_off, nullptr, 0, nullptr, 0,
+                               &n_reads, &n_bases);
+        std::vector<uint8_t> bases(n_bases + 1);
+        std::vector<uint64_t> offsets(n_reads + 1, 0);
+        std::vector<fk_read_stat> stats(n_reads + 1);
+        if (rrc == FK_OK)
+            rrc = fk_reads_csr(text.data(), text.size(), format, (int32_t)min_qual, (int32_t)qual_off, bases.data(), n_bases,
+                               offsets.data(), n_reads, &n_reads, &n_bases);
+        if (rrc == FK_OK)
+            rrc = fk_read_stats(ctx, bases.data(), offsets.data(), n_reads, (uint32_t)min_count, (uint32_t)max_count,
+                                stats.data());
+        if (rrc != FK_OK) {
+            fprintf(stderr, "FASTKMER_CLI_READS: %s\n", fk_last_error());
+            fk_destroy(ctx);
+            return 1;
+        }
+        std::string dir(outdir);
+        for (size_t i = 1; i <= dir.size(); ++i)
+            if (i == dir.size() || dir[i] == '/') (void)mkdir(dir.substr(0, i).c_str(), 0755);
+        const std::string path = dir + (dir.empty() || dir.back() == '/' ? "" : "/") + "read_stats.tsv";
+        FILE *f = fopen(path.c_str(), "w");
+        ok = f != nullptr;
+        for (size_t i = 0; ok && i < n_reads; ++i) {
+            const fk_read_stat &st = stats[i];
+            ok = fprintf(f, "%zu\t%llu\t%u\t%u\t%u\t%u\t%u\t%llu\n", i, (unsigned long long)(offsets[i + 1] - offsets[i]),
+                         st.windows, st.hits, st.min, st.median, st.max, (unsigned long long)st.sum) > 0;
+        }
+        if (f && fclose(f) != 0) ok = false;
+        if (!ok) {
+            fprintf(stderr, "cannot write %s\n", path.c_str());
+            fk_destroy(ctx);
+            return 1;
+        }
+        printf("Read statistics of %zu reads written to %s\n", n_reads, path.c_str());
     }
     fk_destroy(ctx);
     return 0;

@@ -336,6 +336,23 @@ hipError_t launch_query(int KW, const QueryTables &t, const uint64_t *keys, uint
 hipError_t launch_query_seq(int KW, const QueryTables &t, const uint8_t *seq, uint64_t nwin, uint32_t *counts,
                             hipStream_t s);
 
+// ---- per-read profiles of the result (fk_reads.inc).  A batch is bases[n_bases] and offsets[n_reads + 1],
+// ascending from 0 to n_bases; the kernels read n_bases = offsets[n_reads] on the device.
+constexpr int READ_TILE = 4096;  // positions per workgroup tile of k_read_counts (FK_READ_TILE)
+struct ReadStat {                // fk_read_stat
+    uint32_t windows, hits, min, median, max, reserved;
+    uint64_t sum;
+};
+// counts[p] / valid[p] (valid may be null) for every position p < min(n_bases, cap): the count of the
+// canonical k-mer of bases[p, p + k) as launch_query gives it and 1 when the window lies inside one read
+// and holds only A/C/G/T, else 0 and 0.  positions: an upper bound of n_bases if the host has one, else 0.
+hipError_t launch_read_counts(int KW, const QueryTables &t, const uint8_t *bases, const uint64_t *offsets,
+                              uint64_t n_reads, uint64_t positions, uint64_t cap, uint32_t *counts, uint8_t *valid,
+                              hipStream_t s);
+// out[r] over the windows of read r that are valid (valid null: all that exist) and lie below position cap
+hipError_t launch_read_stats(const uint32_t *counts, const uint8_t *valid, const uint64_t *offsets, uint64_t n_reads,
+                             uint64_t cap, int k, uint32_t lo, uint32_t hi, ReadStat *out, hipStream_t s);
+
 // ---- abundance spectrum and count-range views of the bucket-major result (fk_spectrum.inc); the
 // arrays are QueryTables' buckets / dense_off / keys / counts, for either count mode
 // hist[0, n) and *tail (tail may be null) overwritten: hist[c] = distinct k-mers of count c for c < n - 1,

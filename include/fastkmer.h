@@ -425,6 +425,85 @@ int fk_get_bin_range(fk_ctx *ctx, int32_t bin, uint32_t min_count, uint32_t max_
                      uint64_t *keys, uint32_t *counts, size_t cap, size_t *n);
 int fk_write_bins_range(fk_ctx *ctx, const char *out_dir, uint32_t min_count, uint32_t max_count);
 
+/* ---- per-read abundance profiles (no reference counterpart) ----
+ * The counts put back onto reads: for every read, how many of its k-mers are
+ * solid and what their minimum, median and maximum abundance is (the inputs of
+ * kmc_tools filter, normalize-by-median, abundance filters, error trimming and
+ * contamination screens).
+ * A read batch is CSR: bases = uint8[n_bases], the reads' sequence bytes back
+ * to back with no separators; offsets = uint64[n_reads + 1], ascending,
+ * offsets[0] = 0, offsets[n_reads] = n_bases; read i = bases[offsets[i],
+ * offsets[i + 1]).  Reads may be empty or shorter than k.
+ *   fk_reads_csr: host only.  Cuts FASTA or FASTQ text (FK_FORMAT_*) into a
+ *     batch exactly as the count sees it.  FASTA: a read is what follows a
+ *     header line (a non-empty line beginning with '>') up to the next one,
+ *     the '\n' of its lines removed and every other byte kept ('\r', N,
+ *     lowercase and IUPAC codes stay, as invalid positions); lines before the
+ *     first header are no sequence.  FASTQ: the grammar of fk_set_input_format;
+ *     the read is the sequence line (its '\r' under CRLF included), and with
+ *     min_quality > 0 every base whose score is below it is 'N'; malformed
+ *     input gives FK_E_INVALID, the message naming the first malformed record
+ *     (0-based), with *n_reads / *n_bases those of the records before it.
+ *     *n_reads and *n_bases are always set; bases == NULL or offsets == NULL:
+ *     only they (a sizing call).  offsets holds cap_reads + 1 entries;
+ *     FK_E_RANGE when cap_bases or cap_reads is too small.
+ * Window p = bases[p, p + k) exists when it lies wholly inside one read and is
+ * valid when it also holds only A/C/G/T.  Arrays are indexed by base position,
+ * so read i's windows are counts[offsets[i] .. offsets[i] + max(len_i - k + 1, 0)).
+ *   counts[p]: the count of the canonical k-mer of a valid window p, looked up
+ *     exactly as fk_query does (either strand; 0 when absent or when another
+ *     rank owns the k-mer's bin); 0 for every other position.
+ *   valid[p] (may be NULL): 1 exactly for valid windows, the same on every
+ *     rank; the ranks' counts sum to the job's answer.
+ * Preconditions and errors are the lookups': a result of the sorted count
+ * (FK_E_STATE without one, FK_E_INVALID for use_ht == 1).
+ *   fk_read_counts_device: pointers on the context's device (d_counts
+ *     uint32[n_bases], d_valid uint8[n_bases] or NULL; the kernel reads n_bases =
+ *     offsets[n_reads] on the device); only queues on the context's stream: no
+ *     allocation, no synchronisation.  d_bases 16-byte aligned loads fastest.
+ *   fk_read_counts: host pointers, staged in chunks of FASTKMER_QUERY_CHUNK
+ *     positions (each with its k - 1 halo bases and the offsets it touches);
+ *     FK_E_INVALID for offsets that do not ascend from 0.
+ * Per-read statistics over the valid windows, absent k-mers as count 0;
+ * windows == 0: every field 0.  The count range is fk_get_bin_range's
+ * (min_count >= 1, max_count = UINT32_MAX: no upper bound).
+ *   fk_read_stats_of_counts_device: reduces position-indexed device arrays per
+ *     read -- one rank's, or the ranks' summed by the caller; d_valid == NULL:
+ *     every existing window is valid.  Needs only a context (its k), no result.
+ *   fk_read_stats_device: fk_read_counts_device then the reduction, through the
+ *     caller's scratch of fk_read_stats_scratch_bytes(n_bases) bytes (4-byte
+ *     aligned); no allocation, no synchronisation.  Positions beyond a smaller
+ *     scratch are left out of the statistics (nothing is written past it).
+ *   fk_read_stats: host pointers, chunked on whole-read boundaries (a read
+ *     longer than FASTKMER_QUERY_CHUNK positions gets a chunk of its own).
+ *   The two forms that look counts up need every k-mer's count: on a context
+ *   with n_ranks > 1 they return FK_E_INVALID (use fk_read_counts on every
+ *   rank, sum, then fk_read_stats_of_counts_device). */
+#define FK_READ_TILE 4096 /* positions per workgroup tile of the window kernel (tests aim read ends at it) */
+typedef struct fk_read_stat { /* 32 bytes */
+    uint32_t windows;  /* valid windows of the read */
+    uint32_t hits;     /* of them, count in [min_count, max_count] */
+    uint32_t min;      /* over the valid windows */
+    uint32_t median;   /* element (windows - 1) / 2 of the ascending counts */
+    uint32_t max;
+    uint32_t reserved; /* 0 */
+    uint64_t sum;      /* sum of the counts */
+} fk_read_stat;
+int fk_reads_csr(const uint8_t *text, size_t n, int32_t format, int32_t min_quality, int32_t quality_offset,
+                 uint8_t *bases, size_t cap_bases, uint64_t *offsets, size_t cap_reads,
+                 size_t *n_reads, size_t *n_bases);
+int fk_read_counts_device(fk_ctx *ctx, const void *d_bases, const void *d_offsets, size_t n_reads,
+                          void *d_counts, void *d_valid);
+int fk_read_counts(fk_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, size_t n_reads,
+                   uint32_t *counts, uint8_t *valid);
+int fk_read_stats_of_counts_device(fk_ctx *ctx, const void *d_counts, const void *d_valid, const void *d_offsets,
+                                   size_t n_reads, uint32_t min_count, uint32_t max_count, void *d_stats);
+int fk_read_stats_device(fk_ctx *ctx, const void *d_bases, const void *d_offsets, size_t n_reads,
+                         uint32_t min_count, uint32_t max_count, void *d_scratch, size_t scratch_bytes, void *d_stats);
+int fk_read_stats(fk_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, size_t n_reads,
+                  uint32_t min_count, uint32_t max_count, fk_read_stat *stats);
+size_t fk_read_stats_scratch_bytes(size_t n_bases);
+
 /* ---- test hook (no reference counterpart) ----
  * One bucket through the wave-tier count kernel on `device`: the n keys
  * (k <= 32: one word each, n <= 512; 33 <= k <= 63: (hi, lo) pairs, n <= 256)
