@@ -173,6 +173,12 @@ def lib():
         "fk_get_bin_range": (ctypes.c_int, [P, I32, ctypes.c_uint32, ctypes.c_uint32, P, P, SZ,
                                             ctypes.POINTER(SZ)]),
         "fk_write_bins_range": (ctypes.c_int, [P, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32]),
+        "fk_compare": (ctypes.c_int, [P, P, P, SZ, SZ]),
+        "fk_compare_device": (ctypes.c_int, [P, P, P, SZ, SZ]),
+        "fk_bin_sizes_joined": (ctypes.c_int, [P, P, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                               ctypes.c_uint32, P]),
+        "fk_get_bin_joined": (ctypes.c_int, [P, P, I32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                             ctypes.c_uint32, P, P, P, SZ, ctypes.POINTER(SZ)]),
         "fk_map_bin_kmers": (ctypes.c_int, [P, P]),
         "fk_lpt_owners": (ctypes.c_int, [P, I32, I32, P]),
         "fk_set_bin_owners": (ctypes.c_int, [P, P, P]),
@@ -678,6 +684,64 @@ class KmerCounter:
         (set_stream); nothing is allocated or synchronised."""
         _check(lib().fk_spectrum_device(self._h, ctypes.c_void_p(d_hist), int(n),
                                         ctypes.c_void_p(d_tail) if d_tail else None))
+
+    # -- two-sample comparison (fk_compare*, fk_*_joined): this counter is sample A (walked), `other`
+    # sample B (looked up in); same k, m, B, ranks, rank, owners and device, use_ht = False on both
+    def compare(self, other: "KmerCounter", rows: int = 256, cols: int = 256) -> np.ndarray:
+        """The joint count matrix, uint64 of shape (rows, cols): M[a, b] = distinct k-mers with count a
+        here and count b in other (0: absent); the last row / column collect the counts >= rows - 1 /
+        cols - 1; M[0, 0] = 0.  The job's matrix is the sum over the ranks (comm_allreduce)."""
+        m = np.zeros((max(int(rows), 1), max(int(cols), 1)), dtype=np.uint64)
+        _check(lib().fk_compare(self._h, other._h, m.ctypes.data, int(rows), int(cols)))
+        return m
+
+    def compare_ptr(self, other: "KmerCounter", d_matrix: int, rows: int, cols: int) -> None:
+        """fk_compare_device: the matrix into uint64[rows * cols] at device pointer d_matrix,
+        overwritten, queued on this counter's stream (set_stream) behind everything queued on other's;
+        nothing is allocated or synchronised."""
+        _check(lib().fk_compare_device(self._h, other._h, ctypes.c_void_p(d_matrix), int(rows), int(cols)))
+
+    @staticmethod
+    def _join_range(min_count, max_count, other_min, other_max):
+        hi = MAX_COUNT if max_count is None else int(max_count)
+        ohi = MAX_COUNT if other_max is None else int(other_max)
+        rg = (int(min_count), hi, int(other_min), ohi)
+        if not all(0 <= v <= MAX_COUNT for v in rg):
+            raise ValueError("the counts of a joined range are 32-bit")
+        return rg
+
+    def bin_sizes_joined(self, other: "KmerCounter", min_count: int = 1, max_count: int | None = None,
+                         other_min: int = 0, other_max: int | None = None) -> np.ndarray:
+        """Per bin, this counter's k-mers with min_count <= count <= max_count whose count in other
+        lies in [other_min, other_max] (0: absent from other; None: no upper bound)."""
+        out = np.zeros(self.num_bins, dtype=np.uint64)
+        rg = self._join_range(min_count, max_count, other_min, other_max)
+        _check(lib().fk_bin_sizes_joined(self._h, other._h, *rg, out.ctypes.data))
+        return out
+
+    def get_bin_joined(self, other: "KmerCounter", b: int, min_count: int = 1, max_count: int | None = None,
+                       other_min: int = 0, other_max: int | None = None):
+        """(keys, counts, other_counts) of bin b's kept k-mers, in get_bin's order and layout."""
+        n = ctypes.c_size_t(0)
+        rg = self._join_range(min_count, max_count, other_min, other_max)
+        if self._sizes is None:
+            self._sizes = self.bin_sizes()
+        cap = max(int(self._sizes[b]), 1) if 0 <= b < self.num_bins else 1  # the unfiltered size bounds a joined bin
+        kw = 2 if self.k > 32 else 1
+        keys = np.zeros(cap * kw, dtype=np.uint64)
+        counts = np.zeros(cap, dtype=np.uint32)
+        others = np.zeros(cap, dtype=np.uint32)
+        _check(lib().fk_get_bin_joined(self._h, other._h, b, *rg, keys.ctypes.data, counts.ctypes.data,
+                                       others.ctypes.data, cap, ctypes.byref(n)))
+        return keys[:n.value * kw], counts[:n.value], others[:n.value]
+
+    def intersect_bin(self, other: "KmerCounter", b: int):
+        """Bin b's k-mers that other holds too: (keys, counts, other_counts)."""
+        return self.get_bin_joined(other, b, other_min=1)
+
+    def subtract_bin(self, other: "KmerCounter", b: int):
+        """Bin b's k-mers that other lacks: (keys, counts, other_counts), the last all 0."""
+        return self.get_bin_joined(other, b, other_min=0, other_max=0)
 
     # -- lookups in the counted result (fk_query*)
     def query(self, kmers, return_bins: bool = False):

@@ -394,6 +394,11 @@ struct fk_ctx {
     // fk_spectrum: the histogram and its tail sum; fk_get_bin_range: kept k-mers per bucket of one bin
     // and their scan (the filtered bin itself goes through gather_keys / gather_counts)
     DevBuf sp_hist, rg_kept, rg_off;
+    // fk_compare: the matrix before its copy out; fk_get_bin_joined: the kept k-mers' counts in the other
+    // result (beside gather_keys / gather_counts); cmp_ev: "this context's result is complete", recorded
+    // on its stream when another context's comparison looks k-mers up in it
+    DevBuf cmp_mat, gather_other;
+    hipEvent_t cmp_ev = nullptr;
 
     // multi-rank exchange inside the context (fk_comm_init / fk_comm_init_local): the input
     // is emitted in pieces grouped by (destination, local bin) and each piece is exchanged
@@ -695,6 +700,7 @@ FK_EXPORT int fk_create(const fk_config *cfg, fk_ctx **out) {
     }
     e = hipEventCreateWithFlags(&c->tier_ev, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->pin_up_ev, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->cmp_ev, hipEventDisableTiming);
     if (e != hipSuccess) {
         fk_destroy(c);
         return set_err(FK_E_DEVICE, "hipEventCreate: %s", hipGetErrorString(e));
@@ -728,7 +734,7 @@ FK_EXPORT void fk_destroy(fk_ctx *c) {
                       &c->out_keys, &c->out_counts, &c->bucket_unique, &c->dense_off, &c->dense_keys,
                       &c->dense_counts, &c->bin_off, &c->misc, &c->tier_list, &c->mid, &c->sc_total, &c->gather_keys, &c->gather_counts,
                       &c->q_in, &c->q_counts, &c->q_bins, &c->rd_off, &c->rd_valid, &c->rd_stats, &c->sp_hist, &c->rg_kept, &c->rg_off,
-                      &c->sp_base, &c->sp_keys, &c->sp_subs, &c->sp_par, &c->sp_fb, &c->mid_fb};
+                      &c->sp_base, &c->sp_keys, &c->sp_subs, &c->sp_par, &c->sp_fb, &c->mid_fb, &c->cmp_mat, &c->gather_other};
     for (DevBuf *b : bufs) release(*b);
     release(c->fq_ws);
     release(c->fq_info);
@@ -749,6 +755,7 @@ FK_EXPORT void fk_destroy(fk_ctx *c) {
     c->file_pin[1].release();
     if (c->tier_ev) (void)hipEventDestroy(c->tier_ev);
     if (c->pin_up_ev) (void)hipEventDestroy(c->pin_up_ev);
+    if (c->cmp_ev) (void)hipEventDestroy(c->cmp_ev);
     if (c->hold_flag) (void)hipHostFree(c->hold_flag);
     release(c->xsend);
     release(c->xrecv);
@@ -3928,6 +3935,197 @@ FK_EXPORT int fk_write_bins_range(fk_ctx *c, const char *out_dir, uint32_t min_c
                                  max_count, fkeys.as<uint64_t>(), fcounts.as<uint32_t>(), c->stream));
     // the writer ends with the stream drained (its text copy), before the temporaries are released
     return write_bin_text(c, out_dir, fkeys.as<uint64_t>(), fcounts.as<uint32_t>(), D, d_off.as<uint64_t>(), h_off);
+}
+
+// ---------------------------------------------------------------------------
+// two-sample comparison (fk_compare.inc): c's result walked, o's looked up in
+// ---------------------------------------------------------------------------
+
+static int32_t bin_owner(const fk_ctx *c, int32_t b) {
+    return c->custom_owners ? c->h_owner[b] : (int32_t)((uint32_t)b % c->G);
+}
+
+// both contexts count the same k-mers into the same bins of the same rank, and hold a result
+static int compare_pair(const fk_ctx *c, const fk_ctx *o) {
+    if (c->cfg.use_ht || o->cfg.use_ht)
+        return set_err(FK_E_INVALID, "a comparison needs the sorted count (use_ht = 0) on both contexts: a use_ht = 1 "
+                                     "result is in table order");
+    if (c->cfg.k != o->cfg.k) return set_err(FK_E_INVALID, "the contexts differ in k: %d and %d", c->cfg.k, o->cfg.k);
+    if (c->cfg.m != o->cfg.m) return set_err(FK_E_INVALID, "the contexts differ in m: %d and %d", c->cfg.m, o->cfg.m);
+    if (c->Bc != o->Bc) return set_err(FK_E_INVALID, "the contexts differ in their bin count: %d and %d", c->Bc, o->Bc);
+    if (c->G != o->G) return set_err(FK_E_INVALID, "the contexts differ in n_ranks: %u and %u", c->G, o->G);
+    if (c->cfg.rank != o->cfg.rank)
+        return set_err(FK_E_INVALID, "the contexts differ in rank: %d and %d", c->cfg.rank, o->cfg.rank);
+    if (c->device != o->device)
+        return set_err(FK_E_INVALID, "the contexts are on different devices: %d and %d", c->device, o->device);
+    if (c->custom_owners || o->custom_owners)
+        for (int32_t b = 0; b < c->Bc; ++b)
+            if (bin_owner(c, b) != bin_owner(o, b))
+                return set_err(FK_E_INVALID, "the contexts differ in their bin owners: bin %d belongs to rank %d and to rank %d",
+                               b, bin_owner(c, b), bin_owner(o, b));
+    if (!c->have_result || !o->have_result)
+        return set_err(FK_E_STATE, "no result on %s: call fk_finish or fk_reduce first",
+                       !c->have_result ? "the walked context" : "the other context");
+    return FK_OK;
+}
+
+// a context's result as the comparison kernels read it; an empty job: no bucket to walk, every lookup 0
+static int compare_tables(fk_ctx *c, QueryTables &t) {
+    if (c->distinct) return query_tables(c, t);
+    t = QueryTables{};
+    t.fm = c->fm;
+    t.G = 1;
+    t.k = c->cfg.k;
+    t.m = c->cfg.m;
+    return FK_OK;
+}
+
+// c's stream waits for everything queued on o's: o's result arrays are complete when c's kernels read them
+static int compare_order(fk_ctx *c, fk_ctx *o) {
+    if (o == c || o->stream == c->stream) return FK_OK;
+    HIP_TRY(hipEventRecord(o->cmp_ev, o->stream));
+    HIP_TRY(hipStreamWaitEvent(c->stream, o->cmp_ev, 0));
+    return FK_OK;
+}
+
+static int check_matrix_shape(size_t rows, size_t cols) {
+    if (rows < 2 || cols < 2 || rows > 65536 || cols > 65536 || (uint64_t)rows * cols > (1ull << 24))
+        return set_err(FK_E_INVALID, "a comparison matrix has 2 <= rows, cols <= 65536 and rows * cols <= 2^24 (got %zu x %zu)",
+                       rows, cols);
+    return FK_OK;
+}
+
+static uint64_t walk_width(const fk_ctx *c) { return c->spectrum_wide ? ~0ull : c->distinct; }
+
+static int compare_launch(fk_ctx *c, fk_ctx *o, uint64_t *d_matrix, size_t rows, size_t cols) {
+    QueryTables ta, tb;
+    FK_TRY(compare_tables(c, ta));
+    FK_TRY(compare_tables(o, tb));
+    FK_TRY(compare_order(c, o));
+    HIP_TRY(launch_compare(c->KW, ta, tb, walk_width(c), d_matrix, (uint32_t)rows, (uint32_t)cols, false, c->stream));
+    // the k-mers only o holds (every k-mer of c's own result is found in it: nothing to add)
+    if (o != c)
+        HIP_TRY(launch_compare(c->KW, tb, ta, walk_width(o), d_matrix, (uint32_t)rows, (uint32_t)cols, true, c->stream));
+    return FK_OK;
+}
+
+FK_EXPORT int fk_compare_device(fk_ctx *c, fk_ctx *o, void *d_matrix, size_t rows, size_t cols) {
+    if (!c || !o) return set_err(FK_E_INVALID, "null ctx");
+    DeviceGuard dg_(c->device);
+    FK_TRY(check_matrix_shape(rows, cols));
+    FK_TRY(compare_pair(c, o));
+    if (!d_matrix) return set_err(FK_E_INVALID, "null argument");
+    return compare_launch(c, o, static_cast<uint64_t *>(d_matrix), rows, cols);
+}
+
+FK_EXPORT int fk_compare(fk_ctx *c, fk_ctx *o, uint64_t *matrix, size_t rows, size_t cols) {
+    if (!c || !o) return set_err(FK_E_INVALID, "null ctx");
+    DeviceGuard dg_(c->device);
+    FK_TRY(check_matrix_shape(rows, cols));
+    FK_TRY(compare_pair(c, o));
+    if (!matrix) return set_err(FK_E_INVALID, "null argument");
+    const uint64_t bytes = (uint64_t)rows * cols * 8;
+    FK_TRY(ensure(c->cmp_mat, bytes));
+    FK_TRY(compare_launch(c, o, c->cmp_mat.as<uint64_t>(), rows, cols));
+    HIP_TRY(hipMemcpyAsync(matrix, c->cmp_mat.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return FK_OK;
+}
+
+static int check_join_range(uint32_t lo, uint32_t hi, uint32_t olo, uint32_t ohi) {
+    FK_TRY(check_count_range(lo, hi));
+    if (olo > ohi) return set_err(FK_E_INVALID, "other_min %u > other_max %u", olo, ohi);
+    return FK_OK;
+}
+
+FK_EXPORT int fk_bin_sizes_joined(fk_ctx *c, fk_ctx *o, uint32_t min_count, uint32_t max_count, uint32_t other_min,
+                                  uint32_t other_max, uint64_t *out) {
+    if (!c || !o || !out) return set_err(FK_E_INVALID, "null argument");
+    DeviceGuard dg_(c->device);
+    FK_TRY(compare_pair(c, o));
+    FK_TRY(check_join_range(min_count, max_count, other_min, other_max));
+    for (int32_t b = 0; b < c->Bc; ++b) out[b] = 0;
+    if (c->distinct == 0) return FK_OK;
+    QueryTables ta, tb;
+    FK_TRY(compare_tables(c, ta));
+    FK_TRY(compare_tables(o, tb));
+    FK_TRY(compare_order(c, o));
+    // range_offsets with the joined predicate: kept per bucket -> scan -> offsets per local bin
+    DevBuf kept, off, d_off;
+    FreeBufs guard{{&kept, &off, &d_off}};
+    hipStream_t s = c->stream;
+    const uint64_t nb = c->res_nbuckets;
+    const uint32_t nlb = c->nlb;
+    FK_TRY(ensure(kept, nb * 8));
+    FK_TRY(ensure(off, (nb + 1) * 8));
+    FK_TRY(ensure(d_off, ((uint64_t)nlb + 1) * 8));
+    HIP_TRY(launch_join_count(c->KW, ta, tb, min_count, max_count, other_min, other_max, kept.as<uint64_t>(), s));
+    HIP_TRY(scan_excl_sum_u64(kept.as<uint64_t>(), off.as<uint64_t>(), nb, off.as<uint64_t>() + nb, c->ws, s));
+    HIP_TRY(launch_bin_offsets(c->res_fs, off.as<uint64_t>(), nlb, c->res_F, nb, d_off.as<uint64_t>(), s));
+    std::vector<uint64_t> h_off((size_t)nlb + 1, 0);
+    HIP_TRY(hipMemcpyAsync(h_off.data(), d_off.p, ((uint64_t)nlb + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int32_t b = 0; b < c->Bc; ++b)
+        if (owns(c, b)) {
+            const uint32_t lb = local_bin(c, b);
+            out[b] = h_off[lb + 1] - h_off[lb];
+        }
+    return FK_OK;
+}
+
+// One bin joined: the two join kernels over the bin's buckets [q0, q1) only, as fk_get_bin_range.
+FK_EXPORT int fk_get_bin_joined(fk_ctx *c, fk_ctx *o, int32_t bin, uint32_t min_count, uint32_t max_count,
+                                uint32_t other_min, uint32_t other_max, uint64_t *keys, uint32_t *counts,
+                                uint32_t *other_counts, size_t cap, size_t *n) {
+    if (!c || !o || !n) return set_err(FK_E_INVALID, "null argument");
+    DeviceGuard dg_(c->device);
+    FK_TRY(compare_pair(c, o));
+    FK_TRY(check_join_range(min_count, max_count, other_min, other_max));
+    if (bin < 0 || bin >= c->Bc) return set_err(FK_E_RANGE, "bin %d out of [0, %d)", bin, c->Bc);
+    *n = 0;
+    if (!owns(c, bin) || c->distinct == 0) return FK_OK;
+    const uint32_t lb = local_bin(c, bin);
+    if (c->h_bin_off[lb + 1] == c->h_bin_off[lb]) return FK_OK;
+    QueryTables ta, tb;
+    FK_TRY(compare_tables(c, ta));
+    FK_TRY(compare_tables(o, tb));
+    FK_TRY(compare_order(c, o));
+    hipStream_t s = c->stream;
+    uint64_t q[2] = {0, c->res_nbuckets};
+    const uint64_t *fs = c->res_fs;
+    HIP_TRY(hipMemcpyAsync(&q[0], fs + ((uint64_t)lb << c->res_F), 8, hipMemcpyDeviceToHost, s));
+    if (lb + 1 < c->nlb) HIP_TRY(hipMemcpyAsync(&q[1], fs + ((uint64_t)(lb + 1) << c->res_F), 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (q[1] <= q[0] || q[1] > c->res_nbuckets) return FK_OK;
+    const uint64_t nq = q[1] - q[0];
+    FK_TRY(ensure(c->rg_kept, nq * 8));
+    FK_TRY(ensure(c->rg_off, (nq + 1) * 8));
+    ta.buckets += q[0];  // the walk covers the bin's buckets only
+    ta.dense_off += q[0];
+    ta.nbuckets = nq;
+    uint64_t *koff = c->rg_off.as<uint64_t>();
+    HIP_TRY(launch_join_count(c->KW, ta, tb, min_count, max_count, other_min, other_max, c->rg_kept.as<uint64_t>(), s));
+    HIP_TRY(scan_excl_sum_u64(c->rg_kept.as<uint64_t>(), koff, nq, koff + nq, c->ws, s));
+    uint64_t cnt = 0;
+    HIP_TRY(hipMemcpyAsync(&cnt, koff + nq, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *n = (size_t)cnt;
+    if (cnt == 0) return FK_OK;
+    if (cap < cnt)
+        return set_err(FK_E_RANGE, "bin %d has %llu k-mers with counts in [%u, %u] and [%u, %u] in the other result, buffer holds %zu",
+                       bin, (unsigned long long)cnt, min_count, max_count, other_min, other_max, cap);
+    if (!keys && !counts && !other_counts) return FK_OK;
+    FK_TRY(ensure(c->gather_keys, cnt * 8 * c->KW));
+    FK_TRY(ensure(c->gather_counts, cnt * 4));
+    FK_TRY(ensure(c->gather_other, cnt * 4));
+    HIP_TRY(launch_join_compact(c->KW, ta, tb, min_count, max_count, other_min, other_max, koff,
+                                c->gather_keys.as<uint64_t>(), c->gather_counts.as<uint32_t>(),
+                                c->gather_other.as<uint32_t>(), s));
+    if (keys) HIP_TRY(hipMemcpyAsync(keys, c->gather_keys.p, cnt * 8 * c->KW, hipMemcpyDeviceToHost, s));
+    if (counts) HIP_TRY(hipMemcpyAsync(counts, c->gather_counts.p, cnt * 4, hipMemcpyDeviceToHost, s));
+    if (other_counts) HIP_TRY(hipMemcpyAsync(other_counts, c->gather_other.p, cnt * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return FK_OK;
 }
 
 // ---------------------------------------------------------------------------

@@ -25,6 +25,12 @@
 //       settings) are profiled against the result: <outputDir>/read_stats.tsv, one line per read,
 //       "index\tlength\twindows\thits\tmin\tmedian\tmax\tsum" (fk_read_stats; hits counts the k-mers with
 //       FASTKMER_CLI_MIN_COUNT <= count <= FASTKMER_CLI_MAX_COUNT); needs useHT = 0, else a usage error
+//   FASTKMER_CLI_COMPARE=<file>  after the count, <file> is counted in a second context of the same
+//       configuration, input format and quality settings and the two results are compared:
+//       <outputDir>/compare.tsv, "<count in the input>\t<count in file>\t<distinct k-mers>\n" for the nonzero
+//       entries of the joint count matrix (fk_compare), row-major; needs useHT = 0, else a usage error
+//   FASTKMER_CLI_COMPARE_N=<n>  rows = cols = n of that matrix, 2 .. 4096 (default 256): the last row and
+//       column collect the counts >= n - 1
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -134,6 +140,15 @@ int main(int argc, char **argv) {
     if (reads_path && !reads_path[0]) reads_path = nullptr;
     if (reads_path && cfg.use_ht) {
         fprintf(stderr, "FASTKMER_CLI_READS needs the sorted count (useHT = 0): a useHT = 1 result cannot be looked up\n");
+        return usage(argv[0]);
+    }
+    const char *compare_path = getenv("FASTKMER_CLI_COMPARE");
+    if (compare_path && !compare_path[0]) compare_path = nullptr;
+    bool has_cmp_n;
+    uint64_t cmp_n = 256;
+    if (!env_u64("FASTKMER_CLI_COMPARE_N", 2, 4096, &has_cmp_n, &cmp_n)) return usage(argv[0]);
+    if (compare_path && cfg.use_ht) {
+        fprintf(stderr, "FASTKMER_CLI_COMPARE needs the sorted count (useHT = 0): a useHT = 1 result cannot be looked up\n");
         return usage(argv[0]);
     }
     char outdir[4096];
@@ -301,6 +316,64 @@ int main(int argc, char **argv) {
             return 1;
         }
         printf("Read statistics of %zu reads written to %s\n", n_reads, path.c_str());
+    }
+    if (compare_path) {
+        std::vector<uint8_t> text;
+        FILE *in = fopen(compare_path, "rb");
+        bool ok = in != nullptr;
+        if (ok) {
+            uint8_t buf[1 << 16];
+            for (size_t got; (got = fread(buf, 1, sizeof(buf), in)) > 0;) text.insert(text.end(), buf, buf + got);
+            ok = !ferror(in);
+            fclose(in);
+        }
+        if (!ok) {
+            fprintf(stderr, "cannot open %s\n", compare_path);
+            fk_destroy(ctx);
+            return 1;
+        }
+        // the second sample is counted as the job's input was (auto picked the job's format above)
+        fk_ctx *other = nullptr;
+        int crc = fk_create(&cfg, &other);
+        if (crc == FK_OK && format != FK_FORMAT_FASTA)
+            crc = fk_set_input_format(other, format, (int32_t)min_qual, (int32_t)qual_off);
+        if (crc == FK_OK) crc = fk_ingest_reserve(other, text.size());
+        for (size_t off = 0; crc == FK_OK && (off < text.size() || off == 0);) {
+            const size_t len = std::min(window, text.size() - off);
+            crc = fk_ingest(other, text.empty() ? nullptr : text.data() + off, len, off + len >= text.size() ? 1 : 0);
+            off += len;
+            if (text.empty()) break;
+        }
+        if (crc == FK_OK) crc = fk_finish(other);
+        std::vector<uint64_t> mat((size_t)(cmp_n * cmp_n), 0);
+        if (crc == FK_OK) crc = fk_compare(ctx, other, mat.data(), (size_t)cmp_n, (size_t)cmp_n);
+        if (crc != FK_OK) {
+            fprintf(stderr, "FASTKMER_CLI_COMPARE: %s\n", fk_last_error());
+            if (other) fk_destroy(other);
+            fk_destroy(ctx);
+            return 1;
+        }
+        fk_destroy(other);
+        std::string dir(outdir);
+        for (size_t i = 1; i <= dir.size(); ++i)
+            if (i == dir.size() || dir[i] == '/') (void)mkdir(dir.substr(0, i).c_str(), 0755);
+        const std::string path = dir + (dir.empty() || dir.back() == '/' ? "" : "/") + "compare.tsv";
+        FILE *f = fopen(path.c_str(), "w");
+        ok = f != nullptr;
+        size_t lines = 0;
+        for (size_t i = 0; ok && i < mat.size(); ++i) {
+            if (!mat[i]) continue;
+            ok = fprintf(f, "%zu\t%zu\t%llu\n", i / (size_t)cmp_n, i % (size_t)cmp_n, (unsigned long long)mat[i]) > 0;
+            ++lines;
+        }
+        if (f && fclose(f) != 0) ok = false;
+        if (!ok) {
+            fprintf(stderr, "cannot write %s\n", path.c_str());
+            fk_destroy(ctx);
+            return 1;
+        }
+        printf("Comparison with %s (%zu nonzero entries of %llu x %llu) written to %s\n", compare_path, lines,
+               (unsigned long long)cmp_n, (unsigned long long)cmp_n, path.c_str());
     }
     fk_destroy(ctx);
     return 0;

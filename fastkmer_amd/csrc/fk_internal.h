@@ -369,6 +369,25 @@ hipError_t launch_range_compact(int KW, const uint64_t *out_keys, const uint32_t
                                 const uint64_t *dense_off, const uint64_t *keep_off, uint64_t nbuckets, uint32_t lo,
                                 uint32_t hi, uint64_t *fkeys, uint32_t *fcounts, hipStream_t s);
 
+// ---- two results compared (fk_compare.inc).  a: the walked result, b: the one its keys are looked up in
+// (query_count); both bucket-major results of the sorted count with the same k, m, bins, ranks, rank
+// and owners, each with its own buckets and cell bits.  A table with nbuckets == 0 is walked as empty,
+// one with nlb == 0 answers every lookup with 0.
+// only_absent = false (the A-walk): M[0, rows * cols) zeroed, then M[min(ca, rows - 1)][min(cb, cols - 1)]
+// += 1 for every k-mer of a (cb = 0: b lacks it).  only_absent = true (the B-walk, the caller swaps the
+// tables): nothing zeroed, M[0][min(ca, cols - 1)] += 1 for every k-mer of a that b lacks.  rows, cols
+// >= 2; distinct: the k-mers of a (an upper bound will do, it picks the LDS tile's entry width).
+hipError_t launch_compare(int KW, const QueryTables &a, const QueryTables &b, uint64_t distinct, uint64_t *M,
+                          uint32_t rows, uint32_t cols, bool only_absent, hipStream_t s);
+// kept[q] = k-mers of a's bucket q with lo <= ca <= hi and olo <= cb <= ohi
+hipError_t launch_join_count(int KW, const QueryTables &a, const QueryTables &b, uint32_t lo, uint32_t hi,
+                             uint32_t olo, uint32_t ohi, uint64_t *kept, hipStream_t s);
+// ... their keys, ca and cb (each array may be null) in the bucket's order at keep_off[q] (the exclusive
+// scan of kept, a.nbuckets + 1 entries)
+hipError_t launch_join_compact(int KW, const QueryTables &a, const QueryTables &b, uint32_t lo, uint32_t hi,
+                               uint32_t olo, uint32_t ohi, const uint64_t *keep_off, uint64_t *fkeys,
+                               uint32_t *fcounts, uint32_t *fother, hipStream_t s);
+
 // ---- test hook: the 128-bit wave tier's fingerprints cut to `bits` low bits (0: whole), current device
 hipError_t set_fingerprint_bits(int bits);
 

@@ -425,6 +425,57 @@ int fk_get_bin_range(fk_ctx *ctx, int32_t bin, uint32_t min_count, uint32_t max_
                      uint64_t *keys, uint32_t *counts, size_t cap, size_t *n);
 int fk_write_bins_range(fk_ctx *ctx, const char *out_dir, uint32_t min_count, uint32_t max_count);
 
+/* ---- two-sample comparison (no reference counterpart) ----
+ * Two counted sets compared on the device: reads against an assembly (KAT
+ * comp, the spectra-cn plot), sample against sample, a sample against a panel
+ * (kmc_tools simple: intersect, kmers_subtract, counters_subtract).  ctx is
+ * sample A, whose result is walked; other is sample B, in whose result every
+ * k-mer of A is looked up.  ctx == other is allowed.
+ * Compatibility: both contexts must have the same k, m, clamped bin count,
+ * n_ranks and rank, equal fk_bin_owners tables, the same device and use_ht ==
+ * 0 (a use_ht == 1 result cannot be looked up); x may differ.  Anything else
+ * is FK_E_INVALID with a message naming the mismatch.  Both must hold a result
+ * (else FK_E_STATE); an empty result on either side is fine and answers with
+ * zeros, or with only row 0 / column 0 filled.
+ * The calls read both results only: fk_get_bin, fk_write_bins, fk_query and
+ * fk_spectrum on both contexts answer the same before and after them.  None is
+ * collective: each rank answers for the bins it owns.
+ * Streams: the work runs on ctx's stream (the caller's after fk_set_stream).
+ * Before it is queued, ctx's stream is made to wait for an event recorded on
+ * other's stream, so other's result is complete however the caller's streams
+ * are arranged.  While a _device call is outstanding, other must not start a
+ * new job (its first fk_ingest) and must not be destroyed.
+ *   fk_compare: the joint count matrix, row-major uint64[rows][cols], overwritten
+ *     (not accumulated into): matrix[a][b] = the distinct canonical k-mers with
+ *     count a in ctx and count b in other, 0 meaning absent; the last row
+ *     collects the counts >= rows - 1 of ctx, the last column the counts >=
+ *     cols - 1 of other; matrix[0][0] = 0.  So row a >= 1 sums to fk_spectrum's
+ *     entry a of ctx, column b >= 1 to that of other.  2 <= rows, cols <= 65536
+ *     and rows * cols <= 2^24, else FK_E_INVALID.  The job's matrix is the sum
+ *     of the ranks': fk_comm_allreduce_u64 on the matrix gives it.
+ *   fk_compare_device: d_matrix on the contexts' device; only queues the work
+ *     (the walk of ctx, then on the same stream the walk of other for the
+ *     k-mers ctx lacks): no allocation, no synchronisation.
+ * Joined views: a k-mer of ctx is kept when min_count <= its count <= max_count
+ * and other_min <= its count in other <= other_max, all ends inclusive,
+ * UINT32_MAX on an upper end: no upper bound.  min_count >= 1, min_count <=
+ * max_count, other_min <= other_max, else FK_E_INVALID.  other_min = 0 admits
+ * the k-mers other lacks: (other_min, other_max) = (0, 0) is "A minus B",
+ * other_min >= 1 is "A intersect B", and (1, UINT32_MAX, 0, UINT32_MAX) gives
+ * exactly fk_get_bin's keys and counts plus every k-mer's count in other.
+ *   fk_bin_sizes_joined: kept k-mers per bin, all b bins (0 for bins owned by
+ *     other ranks).
+ *   fk_get_bin_joined: fk_get_bin_range's order and buffer rules: *n is always
+ *     set, FK_E_RANGE when cap < *n or the bin is out of [0, b); keys, counts
+ *     and other_counts may each be NULL; a bin of another rank answers 0. */
+int fk_compare(fk_ctx *ctx, fk_ctx *other, uint64_t *matrix, size_t rows, size_t cols);
+int fk_compare_device(fk_ctx *ctx, fk_ctx *other, void *d_matrix, size_t rows, size_t cols);
+int fk_bin_sizes_joined(fk_ctx *ctx, fk_ctx *other, uint32_t min_count, uint32_t max_count,
+                        uint32_t other_min, uint32_t other_max, uint64_t *kept_per_bin);
+int fk_get_bin_joined(fk_ctx *ctx, fk_ctx *other, int32_t bin, uint32_t min_count, uint32_t max_count,
+                      uint32_t other_min, uint32_t other_max, uint64_t *keys, uint32_t *counts,
+                      uint32_t *other_counts, size_t cap, size_t *n);
+
 /* ---- per-read abundance profiles (no reference counterpart) ----
  * The counts put back onto reads: for every read, how many of its k-mers are
  * solid and what their minimum, median and maximum abundance is (the inputs of
