@@ -3,39 +3,27 @@
 // Host orchestration of the device pipeline in fk_kernels.hip.  Replaces the
 // body of SparkBinKmerCounter.executeJob (SparkBinKmerCounter.scala:989-1046):
 // the map closure, the reduceByKey shuffle and the reduce closure.  All device
-// memory is owned by the context and reused across calls (grow-only).
+// memory is owned by the context (fk_ctx.h) and reused across calls (grow-only);
+// the calls that only read a finished result are in fk_views.cpp.
 #include <errno.h>
 #include <fcntl.h>
-#include <hip/hip_runtime.h>
 #include <unistd.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
 #include <sys/stat.h>
 
-#include <algorithm>
 #include <unordered_map>
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
-#include <string>
 #include <thread>
-#include <vector>
 
-#include "../../include/fastkmer.h"
-#include "fk_comm.h"
-#include "fk_internal.h"
+#include "fk_ctx.h"
 #include "fk_split.h"
 
-#define FK_EXPORT extern "C" __attribute__((visibility("default")))
-
-using namespace fk;
-
-namespace {
-
-thread_local std::string g_err;
-
-int set_err(int code, const char *fmt, ...) {
+static thread_local std::string g_err;  // fk_last_error's message
+int fk::set_err(int code, const char *fmt, ...) {
     char buf[1024];
     va_list ap;
     va_start(ap, fmt);
@@ -45,90 +33,7 @@ int set_err(int code, const char *fmt, ...) {
     return code;
 }
 
-#define HIP_TRY(expr)                                                                                \
-    do {                                                                                             \
-        hipError_t e_ = (expr);                                                                      \
-        if (e_ != hipSuccess)                                                                        \
-            return set_err(e_ == hipErrorOutOfMemory ? FK_E_NOMEM : FK_E_DEVICE, "%s failed: %s (%s:%d)", \
-                           #expr, hipGetErrorString(e_), __FILE__, __LINE__);                        \
-    } while (0)
-
-#define FK_TRY(expr)             \
-    do {                         \
-        int r_ = (expr);         \
-        if (r_ != FK_OK) return r_; \
-    } while (0)
-
-// Grow-only pinned host memory: small uploads and read-backs on the hot path go
-// through it (pageable transfers are staged by the runtime, and block the host).
-struct PinBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-    int ensure(size_t need) {
-        if (bytes >= need) return FK_OK;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        bytes = 0;
-        const size_t want = std::max<size_t>(need + need / 4, 4096);
-        if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            return FK_E_NOMEM;
-        }
-        bytes = want;
-        return FK_OK;
-    }
-    void release() {
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        bytes = 0;
-    }
-    template <typename T>
-    T *as() const { return reinterpret_cast<T *>(p); }
-};
-
-struct DevBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-    template <typename T>
-    T *as() const { return reinterpret_cast<T *>(p); }
-};
-
-int ensure(DevBuf &b, size_t bytes) {
-    if (bytes == 0) bytes = 16;
-    if (b.bytes >= bytes) return FK_OK;
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.bytes = 0;
-    // slack for the next job's slightly larger input: an eighth, at most 1 GiB (4 GB of slack on each
-    // k-mer array of a 6.25 GB job would cost more HBM than the reallocations it saves)
-    const size_t want = bytes + std::min<size_t>(bytes / 8, 1ull << 30) + 256;
-    hipError_t e = hipMalloc(&b.p, want);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return set_err(FK_E_NOMEM, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
-    }
-    b.bytes = want;
-    return FK_OK;
-}
-
-void release(DevBuf &b) {
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.bytes = 0;
-}
-
-// Record partition (fk_partition.inc): histogram -> scan -> scatter.
-struct PartBufs {
-    DevBuf H, K, Hs, Ts, KT;              // per-workgroup histograms and destinations (rows), segment sums
-    DevBuf rec, kmer, off, cursor;        // per-part totals / offsets (device), cursor: global path only
-    uint32_t nparts = 0;
-    RecSrc src{};                         // the records counted (part_scatter reads the same)
-    bool global = false;                  // nparts > PART_MAX: global-atomic kernels
-    void release_all() {
-        for (DevBuf *b : {&H, &K, &Hs, &Ts, &KT, &rec, &kmer, &off, &cursor}) release(*b);
-    }
-};
-
+namespace {
 // Counts records and k-mers per part into pb.rec / pb.kmer (device) and keeps
 // what part_scatter needs.
 int part_count(PartBufs &pb, const RecSrc &src, int mode, uint32_t G, const uint32_t *table, uint32_t nparts,
@@ -185,14 +90,6 @@ int part_scatter(PartBufs &pb, int mode, uint32_t G, const uint32_t *table, uint
     return FK_OK;
 }
 
-int32_t clamp_bins(int32_t m, int32_t B) {
-    // test/package.scala:32: Math.min(Math.pow(4, m), max_b).toInt
-    double p = 1.0;
-    for (int i = 0; i < m; ++i) p *= 4.0;
-    const double b = p < (double)B ? p : (double)B;
-    return (int32_t)b;
-}
-
 double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
@@ -208,261 +105,10 @@ static void htrace(const char *what) {
 #endif
 }
 
-// Every exported call that touches the GPU selects the context's device for
-// its duration and restores the caller's current device on return, so one
-// thread may drive contexts on several GPUs and a context may move between
-// threads (e.g. JNI executor threads).
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) {
-            (void)hipGetLastError();
-            prev = -1;
-        }
-        if (dev >= 0 && prev != dev) {
-            (void)hipSetDevice(dev);
-        } else {
-            prev = -1;  // nothing to restore
-        }
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-    DeviceGuard(const DeviceGuard &) = delete;
-    DeviceGuard &operator=(const DeviceGuard &) = delete;
-};
-
 constexpr int FUSED_NT = 512;  // threads per fused map workgroup (256-thread tiles measured 2.5 vs 1.1 ms per GB)
 constexpr uint32_t CHUNK_RECORDS = 16384;  // records per expansion workgroup (never spans two bins)
 
-// The sorted count's shape: cell bits F (super-cells of 2^F2 cells), tiers.
-struct SortedPlan {
-    int F = 1, F2 = 0, F1 = 1;
-    bool tiered = false, two_level = false;
-    uint32_t cap = 2048, wave_cap = WAVE_BUCKET_CAP;
-    uint64_t max_bin = 0;  // the largest bin's k-mers the plan was made for
-};
-
-// A stream and the scan workspace its scans use.  The count's stages take one as a parameter: the
-// context's own (`stream`, `ws`) or the staging stream's (`xstage`, `ws_x`); see main_on / stage_on.
-// A scan owns its workspace from launch to completion, so two streams share one only while their
-// scans are ordered by events.  The side stream (`tier_side`) borrows the main stream's workspace
-// under this rule: its scans (the last piece's bucket cut, the split's sizes) are queued behind a wait
-// for an event recorded on the main stream after that stream's last scan (side_ev[2] after the
-// cell-offset scan of the last piece, or side_ev[3] behind the cut), and the main stream queues no scan
-// again until it has waited for the side stream's work (side_ev[0] after the cut, side_ev[1] after the
-// heavy tiers: the result's scans follow it).
-struct StreamWs {
-    hipStream_t s;
-    ScanWorkspace *ws;
-};
-
 }  // namespace
-
-struct fk_ctx {
-    fk_config cfg{};
-    int32_t Bc = 0;    // b = min(4^m, B)
-    uint32_t G = 1;    // ranks
-    uint32_t nlb = 0;  // local bins: b = rank + G * lb (default placement) or lbin_bin[lb] (custom)
-    // size-aware placement (fk_set_bin_owners): bin -> rank, bin -> local index, local index -> bin
-    bool custom_owners = false;
-    std::vector<int32_t> h_owner, h_lbin_bin;
-    std::vector<uint32_t> h_bin_lbin;
-    DevBuf d_owner, d_local;  // REC_BIN_MASK + 1 entries each (~0u: no part), device copies of the above
-    int W = 2, KW = 1;
-    FastMod fm{};
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    // Test hooks (result-preserving; they steer inputs that FASTA data cannot aim at onto a path):
-    bool force_large = false;  // FASTKMER_DEBUG_LARGE_BUCKETS=1: route every bucket through the streaming path
-    uint32_t cell_target = 0;  // FASTKMER_DEBUG_CELL_TARGET: average keys per cell of the largest bin (0: auto)
-    int mid_parts = -1;        // FASTKMER_DEBUG_MID_PARTS: the 64-bit mid tier's key ranges always (1), the whole
-                               // buckets on the 512-key table always (2), the 1024-key kernel only (0), by size (-1)
-    bool split_retry = false;  // FASTKMER_DEBUG_SPLIT_RETRY: every split bucket cut a second time
-    bool spectrum_wide = false;  // FASTKMER_DEBUG_SPECTRUM_WIDE: the spectrum kernel of results of >= 2^32 k-mers
-    int x2_l1 = 0;             // FASTKMER_X2_L1: level-1 workgroup size (512, 1024; 0 = by fan-out)
-    int fused = 1;             // FASTKMER_FUSED=0: two-kernel map (parse, then signature) for every input
-#ifdef FK_PROBES
-    // Measurement-only (a library built with -DFK_PROBES; wrong results by design):
-    int dbg_phase = 99;        // FASTKMER_DEBUG_PHASE: stop the bucket kernel early
-    int fused_probe = 0;       // FASTKMER_FUSED_PROBE: stop the fused map kernel after a phase
-    int split_map = 0;         // FASTKMER_SPLIT_MAP=1: the map as a parse kernel + a signature-pass kernel
-#endif
-    bool last_map_fused = false;  // the last fk_map used the fused kernel (stats, tests)
-    // grouped emit (fk_set_grouped_emit): send buffer grouped by (destination, local bin)
-    bool grouped = false;
-    uint32_t grp_nlb = 0;                    // parts per destination = ceil(Bc / n_ranks)
-    DevBuf grp_table;                        // bin -> dest * grp_nlb + bin / n_ranks
-    std::vector<uint64_t> grp_rec, grp_kmer; // per part, after fk_map
-    const uint64_t *rsrc = nullptr;          // records the count stage reads (precs, or d_recv when grouped)
-
-    // input
-    // host ingest: bytes are streamed to fasta_own (appended until the next fk_map)
-    bool ingest_fresh = true;        // the next fk_ingest starts a new input
-    bool dev_open = false;           // fk_ingest_device(..., last = 0): the borrowed input is unfinished
-    void *pinned[2] = {nullptr, nullptr};  // staging for pageable sources
-    hipEvent_t pin_ev[2] = {nullptr, nullptr};
-    hipStream_t copy_stream = nullptr;     // H2D of fk_ingest (the map runs on `stream` meanwhile)
-    hipStream_t tier_side = nullptr;       // the count's heavy tiers beside the wave tier, the last piece's cut
-    // [0] cut -> wave tier, [1] heavy tiers -> result, [2] last piece's cell offsets -> cut, [3] -> heavy
-    hipEvent_t side_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t seg_ev = nullptr;           // "segment landed" (copy stream -> map stream)
-    hipEvent_t h2d_ev[2] = {nullptr, nullptr};  // first copy issued / last copy done (timing)
-    // streamed map (fused path): fk_ingest maps every tile whose bytes (and halo) have landed
-    bool pm_active = false;     // the current input is being mapped while it is copied
-    uint64_t pm_tiles = 0;      // tiles [0, pm_tiles) launched
-    bool pm_last_seen = false;  // an fk_ingest with last = 1 launched the final tiles
-    const uint8_t *d_fasta = nullptr;
-    uint64_t n_fasta = 0;
-    DevBuf fasta_own;
-    // FASTQ input (fk_set_input_format): the device input is normalised in place to text the FASTA
-    // parsers read (fk_fastq.inc), record-aligned range after range, each byte once
-    int32_t in_format = FK_FORMAT_FASTA, fq_min_q = 0, fq_q_off = 33;  // the next job's
-    bool job_open = false;      // between a job's first ingest and its fk_map / fk_finish
-    bool fq_job = false;        // the current input is FASTQ
-    uint64_t fq_done = 0;       // the frontier: bytes [0, fq_done) are normalised (and may be mapped)
-    std::vector<uint8_t> fq_tail;  // host copy of the caller's bytes [fq_done, n_fasta) (a record straddling two calls)
-    bool fq_launched = false;   // a normalise launch of this job has been queued
-    DevBuf fq_ws, fq_info;      // launch workspace; the job's records, masked bases, ~(first bad record), overflow
-    PinBuf fq_pin;              // fq_info read back with the map's counters
-    bool fq_have_info = false;  // fk_fastq_info has figures (a FASTQ job was mapped)
-    uint64_t fq_out[3] = {0, 0, UINT64_MAX};
-    std::vector<hipEvent_t> fq_evs;  // begin / end of every normalise launch of the job (fk_debug_fastq_ms)
-    size_t fq_nev = 0;
-
-    // parse + encode
-    DevBuf tile_last_nl, tile_off, npos_dev, codes, valid;
-    // signature
-    DevBuf records, counters, sig_status, sig_kmers;
-    DevBuf tcnt;                  // fused map: records per tile (tiled record layout)
-    DevBuf rec_hdr;               // fused map: every record's header word, in the record's tile slot
-    DevBuf rec_pos;               // fused map: every record's first position in its tile's code stream (u16)
-    DevBuf rec_code;              // fused map: per tile, the tile's 2-bit code stream (map_fused_cslot() words)
-    DevBuf tstat;                 // fused map: per tile (k-mers, positions)
-    DevBuf map_vslots;            // split map: the parse kernel's valid streams for the passes (MAP_VSLOT_TILES tiles)
-    bool rec_tiled = false;       // records: the fused map's tiles (else dense, c->nrec)
-    uint64_t rec_tiles = 0;       // tiles of the tiled layout
-    uint64_t nrec = 0, nkmers = 0;
-    bool mapped = false;
-    // destination partition (n_ranks > 1)
-    std::vector<uint64_t> send_counts;
-    // reduce
-    PartBufs dest, part, binhist;  // record partition by destination rank (fk_map) / by local bin (fk_reduce)
-    DevBuf precs, chunks, bin_chunk_begin;
-    std::vector<uint32_t> h_bcb;  // bin_chunk_begin on the host (the last uploaded chunk table)
-    DevBuf hpieces, hpiece_first, hpiece_tot;  // k_expand_hist_piece: bins split into pieces of chunks
-    DevBuf chunk_nk, chunk_base, lp, cell_total, cell_base, flags, flag_scan, buckets, keys, out_keys, out_counts;
-    DevBuf scratch;
-    DevBuf bucket_unique, dense_off, dense_keys, dense_counts, bin_off, misc, tier_list, mid, sc_total;
-    DevBuf sp_base, sp_keys, sp_subs, sp_par, sp_fb;  // heavy buckets split into sub-buckets
-    DevBuf mid_fb;  // mid-tier buckets left to the 1024-key kernel by the ranges kernel
-    ScanWorkspace ws;
-    // results
-    bool have_result = false;
-    uint64_t distinct = 0;
-    std::vector<uint64_t> h_bin_off;  // [nlb + 1]
-    fk_stats stats{};
-    // events: 0/1 parse, 2/3 signature, 4/5 partition, 6/7 count, 8/9 encode kernel, 10/11 sig kernel
-    hipEvent_t ev[12] = {};
-    double ms_h2d = 0.0;  // last fk_ingest: first copy issued -> last copy done
-    bool ev_parse = false, ev_sig = false, ev_part = false, ev_count = false;
-    std::vector<hipEvent_t> seg_evs;  // fk_ingest, pinned source: one "segment landed" event per segment
-    std::vector<hipEvent_t> map_evs;  // ... and one "segment mapped" event (one rank's staged pieces)
-    std::vector<uint64_t> seg_tiles;  // ... the tiles mapped once that segment's map is done
-    PinBuf pin_up, pin_down;              // staging: chunk tables up, per-bin counts down
-    hipEvent_t pin_up_ev = nullptr;       // the last upload out of pin_up (on whichever stream queued it)
-    bool pin_up_busy = false;             // ... was queued and not yet waited for
-    PinBuf pin_tier;                      // the bucket tiers' sizes, read while the wave tier runs
-    PinBuf file_pin[2];                   // fk_ingest_file_range: the split read in pinned windows
-    hipEvent_t tier_ev = nullptr;         // ... once this copy has landed
-    bool distinct_pending = false;        // the sorted count's distinct total arrives with the bin offsets
-    // The sorted count's result is bucket-major ("gapped"): bucket q's distinct keys ascending at its
-    // first slot buckets[q].begin of res_keys / out_counts, dense_off[q] = their exclusive offset in the
-    // bin-ordered result, bin_off / h_bin_off per bin.  Readers gather a bin's buckets (fk_get_bin) or
-    // the whole result (fk_write_bins).
-    bool gapped = false, dense_ready = false;
-    const uint64_t *res_keys = nullptr;   // okb of the last sorted count (out_keys, or mid)
-    const uint64_t *res_fs = nullptr;     // flag_scan of its bucket cut
-    uint64_t res_nbuckets = 0;
-    int res_F = 0;
-    DevBuf gather_keys, gather_counts;    // fk_get_bin's gather of one bin
-    // fk_query / fk_query_sequence: staging of one chunk's keys (or bases), counts and bins
-    DevBuf q_in, q_counts, q_bins;
-    // fk_read_counts / fk_read_stats: one chunk's offsets, valid flags and statistics (bases in q_in, counts in q_counts)
-    DevBuf rd_off, rd_valid, rd_stats;
-    // fk_spectrum: the histogram and its tail sum; fk_get_bin_range: kept k-mers per bucket of one bin
-    // and their scan (the filtered bin itself goes through gather_keys / gather_counts)
-    DevBuf sp_hist, rg_kept, rg_off;
-    // fk_compare: the matrix before its copy out; fk_get_bin_joined: the kept k-mers' counts in the other
-    // result (beside gather_keys / gather_counts); cmp_ev: "this context's result is complete", recorded
-    // on its stream when another context's comparison looks k-mers up in it
-    DevBuf cmp_mat, gather_other;
-    hipEvent_t cmp_ev = nullptr;
-
-    // multi-rank exchange inside the context (fk_comm_init / fk_comm_init_local): the input
-    // is emitted in pieces grouped by (destination, local bin) and each piece is exchanged
-    // while the next one is still being copied in; fk_finish sends the last piece, then
-    // counts every received segment (the reduceByKey shuffle of SBKC:1034-1042)
-    // staged pieces (one rank, or the received segments with a communicator; sorted count, k <= 63):
-    // each piece of the input is partitioned and expanded into its own key array while later pieces
-    // land; the job's buckets are counted once over every piece's keys (no per-piece count, no merge)
-    bool pieces_void = false;     // a fallback or a retract: the job is counted whole at the end
-    uint64_t tiles_counted = 0;   // one rank: tiled records [0, tiles_counted) staged
-    uint64_t job_bytes = 0;       // one rank: the job's input size when one fk_ingest call holds it all, or
-                                  // announced by fk_ingest_reserve (0: unknown)
-    uint64_t reserve_bytes = 0;   // fk_ingest_reserve's size for the next job
-    size_t segs_counted = 0;      // with a communicator: received segments [0, segs_counted) staged
-    std::vector<double> st_cuts{0.4, 0.7, 0.9};  // piece ends of a staged job (FASTKMER_PIECE_CUTS; 45 / 70 / 85 % measured 22.84 vs 22.77 ms)
-    // ... of a 64-bit job of >= 4 GB without FASTKMER_PIECE_CUTS: five pieces, the last 7 % (configs[2]
-    // load 146.2 -> 145.4 ms, profiles/r06z_five_pieces.txt; configs[1]'s 1 GB keeps four)
-    std::vector<double> st_cuts5{0.38, 0.64, 0.82, 0.93};
-    bool cuts_env = false;
-    // ... with a communicator: earlier, a received piece lands a step's partition and transfer later
-    // (one in-process rank at the configs[2] load: 153.2-153.7 ms against 156.1-159.4 with the local
-    // cuts, profiles/r05z_xch_cuts_seg_ab.txt)
-    std::vector<double> xst_cuts{0.35, 0.65, 0.84};
-    uint32_t st_np = 0;                          // pieces expanded in the current job
-    uint32_t st_cut = 0;                         // one rank: st_cuts passed in the current job
-    SortedPlan st_plan;                          // the job's cells (fixed by its first piece)
-    uint64_t st_kmers = 0;                       // k-mers expanded so far
-    DevBuf st_keys[STAGE_MAXP], st_cb[STAGE_MAXP], st_total, piece_starts;
-    hipEvent_t st_ev[4 * STAGE_MAXP] = {};       // per piece: partition begin / end, expansion begin / end
-
-    fk::Comm *comm = nullptr;
-    hipStream_t comm_stream = nullptr;
-    uint32_t *hold_flag = nullptr;               // fk_debug_comm_hold: host-mapped release flag
-    // staging of received segments on its own stream (each waits for its step's transfer, so the map
-    // stream never does) with its own scan workspace; the count waits for it
-    hipStream_t xstage = nullptr;
-    hipEvent_t xstage_ev = nullptr;
-    ScanWorkspace ws_x;
-    StreamWs main_on() { return StreamWs{stream, &ws}; }
-    StreamWs stage_on() { return StreamWs{xstage, &ws_x}; }
-    hipEvent_t emit_ev = nullptr;                // map stream: a piece's send records are written
-    std::vector<hipEvent_t> xev;                 // comm stream: begin / end of every piece's transfer
-    uint64_t piece_bytes = 512ull << 20;         // FASTKMER_PIECE_BYTES: FASTA bytes per piece (with a
-                                                 // communicator: a tenth of a known job, 128 MB .. 1 GB)
-    bool piece_bytes_set = false;
-    uint64_t ingest_seg = 32ull << 20;           // FASTKMER_INGEST_SEG: H2D segment of a pinned source
-    DevBuf xsend, xrecv;                         // send ring (pieces in flight), received records
-    struct XSeg {                                // received records of one (piece, sender)
-        uint64_t off;                            // first record in xrecv
-        int32_t sender;
-        uint64_t step;                           // the exchange step that delivered it
-        std::vector<uint64_t> rec, kmer;         // per local bin
-    };
-    struct Xch {
-        bool open = false;           // a job's exchange has started (pieces sent)
-        bool sent_final = false;     // this rank has sent its last piece
-        bool all_final = false;      // every rank has sent its last piece
-        bool stop_pieces = false;    // the fused map fell back: the rest goes in fk_finish, earlier pieces retracted
-        uint64_t tiles_sent = 0;     // tiled records [0, tiles_sent) emitted in pieces
-        uint64_t send_used = 0, recv_used = 0;  // records
-        uint64_t pieces = 0, bytes_sent = 0, bytes_received = 0, expect_bytes = 0;
-        std::vector<XSeg> segs;
-    } xch;
-};
 
 // ---------------------------------------------------------------------------
 // host-only helpers
@@ -732,10 +378,10 @@ FK_EXPORT void fk_destroy(fk_ctx *c) {
                       &c->chunk_base, &c->lp, &c->scratch,
                       &c->cell_total, &c->cell_base, &c->flags, &c->flag_scan, &c->buckets, &c->keys,
                       &c->out_keys, &c->out_counts, &c->bucket_unique, &c->dense_off, &c->dense_keys,
-                      &c->dense_counts, &c->bin_off, &c->misc, &c->tier_list, &c->mid, &c->sc_total, &c->gather_keys, &c->gather_counts,
-                      &c->q_in, &c->q_counts, &c->q_bins, &c->rd_off, &c->rd_valid, &c->rd_stats, &c->sp_hist, &c->rg_kept, &c->rg_off,
-                      &c->sp_base, &c->sp_keys, &c->sp_subs, &c->sp_par, &c->sp_fb, &c->mid_fb, &c->cmp_mat, &c->gather_other};
+                      &c->dense_counts, &c->bin_off, &c->misc, &c->tier_list, &c->mid, &c->sc_total,
+                      &c->sp_base, &c->sp_keys, &c->sp_subs, &c->sp_par, &c->sp_fb, &c->mid_fb};
     for (DevBuf *b : bufs) release(*b);
+    c->vw.release_all();
     release(c->fq_ws);
     release(c->fq_info);
     for (auto &e : c->fq_evs)
@@ -1442,12 +1088,6 @@ FK_EXPORT int fk_synth_fasta_device(fk_ctx *c, uint64_t first_read, uint64_t n_r
 // map side: parse + encode + signature + records (+ destination histogram)
 // ---------------------------------------------------------------------------
 
-
-static const uint32_t *owner_table(const fk_ctx *c) { return c->custom_owners ? c->d_owner.as<uint32_t>() : nullptr; }
-static const uint32_t *local_table(const fk_ctx *c) { return c->custom_owners ? c->d_local.as<uint32_t>() : nullptr; }
-static int32_t global_bin(const fk_ctx *c, uint32_t lb) {
-    return c->custom_owners ? c->h_lbin_bin[lb] : (int32_t)(c->cfg.rank + lb * c->G);
-}
 
 // Fused parse + signature (k_map_fused): FASTA bytes to records in one kernel.
 // *ok = false when a tile raised the fallback flag (the caller then maps with
@@ -2850,7 +2490,7 @@ static int note_held(fk_ctx *c, int rc) {
     FK_HELD(flags); FK_HELD(flag_scan); FK_HELD(cell_total); FK_HELD(cell_base); FK_HELD(dense_keys);
     FK_HELD(dense_counts); FK_HELD(bucket_unique);
     FK_HELD(sp_keys); FK_HELD(sp_subs); FK_HELD(xsend); FK_HELD(xrecv);
-    FK_HELD(gather_keys); FK_HELD(part.K); FK_HELD(part.KT); FK_HELD(dest.K); FK_HELD(dest.KT);
+    add("gather_keys", c->vw.gather_keys); FK_HELD(part.K); FK_HELD(part.KT); FK_HELD(dest.K); FK_HELD(dest.KT);
 #undef FK_HELD
     std::vector<std::string> piece_names(STAGE_MAXP);
     for (int p = 0; p < STAGE_MAXP; ++p) {
@@ -3387,197 +3027,6 @@ FK_EXPORT int fk_balance_bins_file(fk_ctx *c, const char *path, int32_t world, i
     return rc && c->comm ? comm_fail(c, rc) : rc;
 }
 
-// ---------------------------------------------------------------------------
-// results
-// ---------------------------------------------------------------------------
-
-static bool owns(const fk_ctx *c, int32_t b) {
-    if (b < 0 || b >= c->Bc) return false;
-    return c->custom_owners ? c->h_owner[b] == c->cfg.rank : (uint32_t)b % c->G == (uint32_t)c->cfg.rank;
-}
-static uint32_t local_bin(const fk_ctx *c, int32_t b) { return c->custom_owners ? c->h_bin_lbin[b] : (uint32_t)b / c->G; }
-
-FK_EXPORT int fk_bin_sizes(fk_ctx *c, uint64_t *out) {
-    if (!c || !out) return set_err(FK_E_INVALID, "null argument");
-    if (!c->have_result) return set_err(FK_E_STATE, "no result: call fk_finish or fk_reduce first");
-    for (int32_t b = 0; b < c->Bc; ++b) {
-        if (owns(c, b)) {
-            const uint32_t lb = local_bin(c, b);
-            out[b] = c->h_bin_off[lb + 1] - c->h_bin_off[lb];
-        } else {
-            out[b] = 0;
-        }
-    }
-    return FK_OK;
-}
-
-// A bucket-major result made dense (fk_write_bins): the buckets' outputs compacted in bin order.
-static int materialize_dense(fk_ctx *c) {
-    if (!c->gapped || c->dense_ready) return FK_OK;
-    hipStream_t s = c->stream;
-    FK_TRY(ensure(c->dense_keys, c->distinct * 8 * c->KW));
-    FK_TRY(ensure(c->dense_counts, c->distinct * 4));
-    HIP_TRY(launch_bucket_compact(c->KW, c->res_keys, c->out_counts.as<uint32_t>(), c->buckets.as<Bucket>(),
-                                  c->res_nbuckets, c->dense_off.as<uint64_t>(), c->dense_keys.as<uint64_t>(),
-                                  c->dense_counts.as<uint32_t>(), s));
-    HIP_TRY(hipStreamSynchronize(s));
-    c->dense_ready = true;
-    return FK_OK;
-}
-
-// One local bin of a bucket-major result into dst (device): its buckets [q0, q1) -- the bin's first
-// cell starts a bucket, so q0 = flag_scan[lb << F] -- compacted at dense_off[q] - dense_off[q0].
-static int gather_bin(fk_ctx *c, uint32_t lb, uint64_t *dkeys, uint32_t *dcounts) {
-    hipStream_t s = c->stream;
-    uint64_t q[2] = {0, c->res_nbuckets};
-    const uint64_t *fs = c->res_fs;
-    HIP_TRY(hipMemcpyAsync(&q[0], fs + ((uint64_t)lb << c->res_F), 8, hipMemcpyDeviceToHost, s));
-    if (lb + 1 < c->nlb) HIP_TRY(hipMemcpyAsync(&q[1], fs + ((uint64_t)(lb + 1) << c->res_F), 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    const uint64_t d0 = c->h_bin_off[lb];
-    if (q[1] > q[0])
-        HIP_TRY(launch_bucket_compact(c->KW, c->res_keys, c->out_counts.as<uint32_t>(), c->buckets.as<Bucket>() + q[0],
-                                      q[1] - q[0], c->dense_off.as<uint64_t>() + q[0], dkeys - d0 * c->KW, dcounts - d0, s));
-    return FK_OK;
-}
-
-FK_EXPORT int fk_get_bin(fk_ctx *c, int32_t bin, uint64_t *keys, uint32_t *counts, size_t cap, size_t *n) {
-    if (!c || !n) return set_err(FK_E_INVALID, "null argument");
-    DeviceGuard dg_(c->device);
-    if (!c->have_result) return set_err(FK_E_STATE, "no result: call fk_finish or fk_reduce first");
-    if (bin < 0 || bin >= c->Bc) return set_err(FK_E_RANGE, "bin %d out of [0, %d)", bin, c->Bc);
-    if (!owns(c, bin)) {
-        *n = 0;
-        return FK_OK;
-    }
-    const uint32_t lb = local_bin(c, bin);
-    const uint64_t b0 = c->h_bin_off[lb], cnt = c->h_bin_off[lb + 1] - b0;
-    *n = (size_t)cnt;
-    if (cnt == 0) return FK_OK;
-    if (cap < cnt) return set_err(FK_E_RANGE, "bin %d has %llu k-mers, buffer holds %zu", bin, (unsigned long long)cnt, cap);
-    if (c->gapped && !c->dense_ready) {
-        FK_TRY(ensure(c->gather_keys, cnt * 8 * c->KW));
-        FK_TRY(ensure(c->gather_counts, cnt * 4));
-        FK_TRY(gather_bin(c, lb, c->gather_keys.as<uint64_t>(), c->gather_counts.as<uint32_t>()));
-        if (keys)
-            HIP_TRY(hipMemcpyAsync(keys, c->gather_keys.p, cnt * 8 * c->KW, hipMemcpyDeviceToHost, c->stream));
-        if (counts) HIP_TRY(hipMemcpyAsync(counts, c->gather_counts.p, cnt * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        return FK_OK;
-    }
-    if (keys)
-        HIP_TRY(hipMemcpy(keys, c->dense_keys.as<uint64_t>() + b0 * c->KW, cnt * 8 * c->KW, hipMemcpyDeviceToHost));
-    if (counts) HIP_TRY(hipMemcpy(counts, c->dense_counts.as<uint32_t>() + b0, cnt * 4, hipMemcpyDeviceToHost));
-    return FK_OK;
-}
-
-// ---------------------------------------------------------------------------
-// lookups in the counted result (fk_query.inc)
-// ---------------------------------------------------------------------------
-
-// keys (or windows) per staged chunk of fk_query / fk_query_sequence: FASTKMER_QUERY_CHUNK, default 16 Mi
-static uint64_t query_chunk() {
-    const char *v = getenv("FASTKMER_QUERY_CHUNK");
-    const uint64_t n = v && v[0] ? strtoull(v, nullptr, 10) : 0;
-    return n ? n : 16ull << 20;
-}
-
-// the sorted count's bucket-major arrays as the lookup kernel reads them
-static int query_tables(fk_ctx *c, QueryTables &t) {
-    if (c->cfg.use_ht)
-        return set_err(FK_E_INVALID, "lookups need the sorted count (use_ht = 0): a use_ht = 1 result is in table order");
-    if (!c->have_result || !c->gapped) return set_err(FK_E_STATE, "no result: call fk_finish or fk_reduce first");
-    t.flag_scan = c->res_fs;
-    t.buckets = c->buckets.as<Bucket>();
-    t.dense_off = c->dense_off.as<uint64_t>();
-    t.keys = c->res_keys;
-    t.counts = c->out_counts.as<uint32_t>();
-    t.owner = owner_table(c);
-    t.local = local_table(c);
-    t.nbuckets = c->res_nbuckets;
-    t.fm = c->fm;
-    t.G = c->G;
-    t.rank = (uint32_t)c->cfg.rank;
-    t.nlb = c->nlb;
-    t.k = c->cfg.k;
-    t.m = c->cfg.m;
-    t.F = c->res_F;
-    return FK_OK;
-}
-
-FK_EXPORT int fk_kmer_bin(const fk_config *cfg, const uint64_t *key, int32_t *bin) {
-    if (!cfg || !key || !bin) return set_err(FK_E_INVALID, "null argument");
-    FK_TRY(fk_config_validate(cfg));
-    const int k = cfg->k;
-    const KmerKey f = k > 32 ? KmerKey{key[0], key[1]} : KmerKey{0, key[0]};
-    if (!key_is_kmer(f, k)) return set_err(FK_E_INVALID, "the key has a bit set above bit 2k - 1 = %d", 2 * k - 1);
-    const uint32_t sig = k > 32 ? kmer_signature<true>(f, revcomp_key<true>(f, k), k, cfg->m)
-                                : kmer_signature<false>(f, revcomp_key<false>(f, k), k, cfg->m);
-    *bin = (int32_t)bin_of_signature(sig, make_fastmod((uint32_t)clamp_bins(cfg->m, cfg->B)));
-    return FK_OK;
-}
-
-FK_EXPORT int fk_query_device(fk_ctx *c, const void *d_keys, size_t n, void *d_counts, void *d_bins) {
-    if (!c) return set_err(FK_E_INVALID, "null ctx");
-    DeviceGuard dg_(c->device);
-    QueryTables t;
-    FK_TRY(query_tables(c, t));
-    if (n == 0) return FK_OK;
-    if (!d_keys || !d_counts) return set_err(FK_E_INVALID, "null argument");
-    HIP_TRY(launch_query(c->KW, t, static_cast<const uint64_t *>(d_keys), n, static_cast<uint32_t *>(d_counts),
-                         static_cast<int32_t *>(d_bins), c->stream));
-    return FK_OK;
-}
-
-FK_EXPORT int fk_query(fk_ctx *c, const uint64_t *keys, size_t n, uint32_t *counts, int32_t *bins) {
-    if (!c) return set_err(FK_E_INVALID, "null ctx");
-    DeviceGuard dg_(c->device);
-    QueryTables t;
-    FK_TRY(query_tables(c, t));
-    if (n == 0) return FK_OK;
-    if (!keys || !counts) return set_err(FK_E_INVALID, "null argument");
-    hipStream_t s = c->stream;
-    const size_t chunk = (size_t)std::min<uint64_t>(query_chunk(), n), kb = (size_t)c->KW * 8;
-    FK_TRY(ensure(c->q_in, chunk * kb));
-    FK_TRY(ensure(c->q_counts, chunk * 4));
-    if (bins) FK_TRY(ensure(c->q_bins, chunk * 4));
-    for (size_t at = 0; at < n; at += chunk) {
-        const size_t nc = std::min(chunk, n - at);
-        HIP_TRY(hipMemcpyAsync(c->q_in.p, keys + at * c->KW, nc * kb, hipMemcpyHostToDevice, s));
-        HIP_TRY(launch_query(c->KW, t, c->q_in.as<uint64_t>(), nc, c->q_counts.as<uint32_t>(),
-                             bins ? c->q_bins.as<int32_t>() : nullptr, s));
-        HIP_TRY(hipMemcpyAsync(counts + at, c->q_counts.p, nc * 4, hipMemcpyDeviceToHost, s));
-        if (bins) HIP_TRY(hipMemcpyAsync(bins + at, c->q_bins.p, nc * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));  // the staging buffers are free for the next chunk
-    }
-    return FK_OK;
-}
-
-FK_EXPORT int fk_query_sequence(fk_ctx *c, const uint8_t *seq, size_t len, uint32_t *counts, size_t cap, size_t *n) {
-    if (!c || !n) return set_err(FK_E_INVALID, "null argument");
-    DeviceGuard dg_(c->device);
-    QueryTables t;
-    FK_TRY(query_tables(c, t));
-    const size_t k = (size_t)c->cfg.k, nwin = len >= k ? len - k + 1 : 0;
-    *n = nwin;
-    if (!counts || nwin == 0) return FK_OK;
-    if (cap < nwin) return set_err(FK_E_RANGE, "the sequence has %zu windows, buffer holds %zu", nwin, cap);
-    if (!seq) return set_err(FK_E_INVALID, "null argument");
-    hipStream_t s = c->stream;
-    // windows [at, at + nc) read the bases [at, at + nc + k - 1): packed on the device (k_query_seq)
-    const size_t chunk = (size_t)std::min<uint64_t>(query_chunk(), nwin);
-    FK_TRY(ensure(c->q_in, chunk + k - 1));
-    FK_TRY(ensure(c->q_counts, chunk * 4));
-    for (size_t at = 0; at < nwin; at += chunk) {
-        const size_t nc = std::min(chunk, nwin - at);
-        HIP_TRY(hipMemcpyAsync(c->q_in.p, seq + at, nc + k - 1, hipMemcpyHostToDevice, s));
-        HIP_TRY(launch_query_seq(c->KW, t, c->q_in.as<uint8_t>(), nc, c->q_counts.as<uint32_t>(), s));
-        HIP_TRY(hipMemcpyAsync(counts + at, c->q_counts.p, nc * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-    }
-    return FK_OK;
-}
-
 // Test hooks of the failure semantics (fastkmer.h): hold every stream the context's collectives run
 // on with a kernel spinning on a host-mapped flag, so the next collective waits on a stream that does
 // not drain; release it from any thread.
@@ -3646,7 +3095,7 @@ FK_EXPORT int fk_debug_wave_count(int32_t device, int32_t k, int32_t F, uint32_t
             return set_err(FK_E_RANGE, "key %u lies outside cells [%u, %u)", i, c0, c1);
     }
     DeviceGuard dg_(device);
-    DevBuf dk, dok, doc, du, db;
+    TempBuf dk, dok, doc, du, db;
     FK_TRY(ensure(dk, (uint64_t)n * 8 * KW));
     FK_TRY(ensure(dok, (uint64_t)n * 8 * KW));
     FK_TRY(ensure(doc, (uint64_t)n * 4));
@@ -3668,7 +3117,6 @@ FK_EXPORT int fk_debug_wave_count(int32_t device, int32_t k, int32_t F, uint32_t
     if (e != hipSuccess) rc = set_err(FK_E_DEVICE, "%s", hipGetErrorString(e));
     else if (U > n) rc = set_err(FK_E_INVALID, "bucket reported %llu distinct keys of %u", (unsigned long long)U, n);
     *n_out = (uint32_t)U;
-    release(dk), release(dok), release(doc), release(du), release(db);
     return rc;
 }
 
@@ -3688,716 +3136,6 @@ FK_EXPORT int fk_debug_map_cycles(uint64_t *out16, int32_t reset) {
 FK_EXPORT int fk_get_stats(fk_ctx *c, fk_stats *out) {
     if (!c || !out) return set_err(FK_E_INVALID, "null argument");
     *out = c->stats;
-    return FK_OK;
-}
-
-static int mkdir_p(const std::string &path) {
-    std::string cur;
-    for (size_t i = 0; i < path.size(); ++i) {
-        cur.push_back(path[i]);
-        if ((path[i] == '/' && i > 0) || i + 1 == path.size()) {
-            if (mkdir(cur.c_str(), 0755) != 0 && errno != EEXIST) return -1;
-        }
-    }
-    return 0;
-}
-
-// Bin files (writers SBKC:550-606 / 715-734) of D dense lines (device keys / counts in bin order,
-// bin_off / h_bin_off their nlb + 1 offsets per local bin on the device / host): the text is
-// formatted on the device (fk_format.inc), copied to the host once and written one file per bin.
-static int write_bin_text(fk_ctx *c, const char *out_dir, const uint64_t *keys, const uint32_t *counts, uint64_t D,
-                          const uint64_t *bin_off, const std::vector<uint64_t> &h_bin_off) {
-    hipStream_t s = c->stream;
-    const uint32_t nlb = c->nlb;
-    const int eof = c->cfg.use_ht == 0;
-    if (D == 0) return FK_OK;  // no k-mers: no bin files
-    DevBuf len, off, bbytes, text;
-    struct Free {
-        DevBuf *b[4];
-        ~Free() {
-            for (DevBuf *x : b) release(*x);
-        }
-    } guard{{&len, &off, &bbytes, &text}};
-    FK_TRY(ensure(len, D * 4));
-    FK_TRY(ensure(off, (D + 1) * 8));
-    FK_TRY(ensure(bbytes, ((uint64_t)nlb + 1) * 8));
-    HIP_TRY(launch_format_lens(counts, D, c->cfg.k, bin_off, nlb, eof, len.as<uint32_t>(), s));
-    HIP_TRY(scan_excl_sum_u32_to_u64(len.as<uint32_t>(), off.as<uint64_t>(), D, off.as<uint64_t>() + D, c->ws, s));
-    HIP_TRY(launch_gather_u64(off.as<uint64_t>(), bin_off, (uint64_t)nlb + 1, bbytes.as<uint64_t>(), s));
-    std::vector<uint64_t> bb(nlb + 1, 0);
-    HIP_TRY(hipMemcpyAsync(bb.data(), bbytes.p, ((uint64_t)nlb + 1) * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    const uint64_t T = bb[nlb];
-    FK_TRY(ensure(text, T + 16));
-    HIP_TRY(launch_format_lines(c->KW, keys, counts, D, c->cfg.k, off.as<uint64_t>(), text.as<uint8_t>(), s));
-    uint8_t *host = nullptr;
-    if (T) {
-        HIP_TRY(hipHostMalloc((void **)&host, T, hipHostMallocDefault));
-        const hipError_t e = hipMemcpyAsync(host, text.p, T, hipMemcpyDeviceToHost, s);
-        const hipError_t e2 = e == hipSuccess ? hipStreamSynchronize(s) : e;
-        if (e2 != hipSuccess) {
-            (void)hipHostFree(host);
-            return set_err(FK_E_DEVICE, "copying the bin text to the host: %s", hipGetErrorString(e2));
-        }
-    }
-    const std::string dir(out_dir);
-    const unsigned nth = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-    std::vector<int> errs(nth, 0);
-    std::vector<std::thread> th;
-    for (unsigned t = 0; t < nth; ++t) {
-        th.emplace_back([&, t]() {
-            for (uint32_t lb = t; lb < nlb; lb += nth) {
-                if (h_bin_off[lb + 1] == h_bin_off[lb]) continue;  // empty bins have no file
-                const std::string path = dir + "/bin" + std::to_string(global_bin(c, lb));
-                FILE *f = fopen(path.c_str(), "wb");
-                const size_t nb = (size_t)(bb[lb + 1] - bb[lb]);
-                if (!f || fwrite(host + bb[lb], 1, nb, f) != nb) errs[t] = 1;
-                if (f && fclose(f) != 0) errs[t] = 1;
-            }
-        });
-    }
-    for (auto &x : th) x.join();
-    if (host) (void)hipHostFree(host);
-    for (int e : errs)
-        if (e) return set_err(FK_E_IO, "writing bin files under %s failed", out_dir);
-    return FK_OK;
-}
-
-FK_EXPORT int fk_write_bins(fk_ctx *c, const char *out_dir) {
-    if (!c || !out_dir) return set_err(FK_E_INVALID, "null argument");
-    DeviceGuard dg_(c->device);
-    if (!c->have_result) return set_err(FK_E_STATE, "no result: call fk_finish or fk_reduce first");
-    if (mkdir_p(out_dir) != 0) return set_err(FK_E_IO, "cannot create %s: %s", out_dir, strerror(errno));
-    if (c->distinct == 0) return FK_OK;  // no k-mers: no bin files
-    FK_TRY(materialize_dense(c));
-    return write_bin_text(c, out_dir, c->dense_keys.as<uint64_t>(), c->dense_counts.as<uint32_t>(), c->distinct,
-                          c->bin_off.as<uint64_t>(), c->h_bin_off);
-}
-
-// ---------------------------------------------------------------------------
-// abundance spectrum and count-range views of the counted result (fk_spectrum.inc); either count mode
-// ---------------------------------------------------------------------------
-
-static int result_ready(const fk_ctx *c) {
-    if (!c->have_result) return set_err(FK_E_STATE, "no result: call fk_finish or fk_reduce first");
-    if (c->distinct && !c->gapped) return set_err(FK_E_STATE, "the result is not bucket-major");
-    return FK_OK;
-}
-
-static int check_count_range(uint32_t lo, uint32_t hi) {
-    if (lo == 0) return set_err(FK_E_INVALID, "min_count must be >= 1 (no k-mer of the result has count 0)");
-    if (lo > hi) return set_err(FK_E_INVALID, "min_count %u > max_count %u", lo, hi);
-    return FK_OK;
-}
-
-static int spectrum_launch(fk_ctx *c, uint64_t *d_hist, size_t n, uint64_t *d_tail) {
-    // an empty job has no buckets: the launcher only clears the outputs
-    HIP_TRY(launch_spectrum(c->out_counts.as<uint32_t>(), c->buckets.as<Bucket>(), c->dense_off.as<uint64_t>(),
-                            c->distinct ? c->res_nbuckets : 0, c->spectrum_wide ? ~0ull : c->distinct, d_hist, n, d_tail,
-                            c->stream));
-    return FK_OK;
-}
-
-FK_EXPORT int fk_spectrum_device(fk_ctx *c, void *d_hist, size_t n, void *d_tail_kmers) {
-    if (!c) return set_err(FK_E_INVALID, "null ctx");
-    DeviceGuard dg_(c->device);
-    FK_TRY(result_ready(c));
-    if (n < 2) return set_err(FK_E_INVALID, "a spectrum has n >= 2 entries");
-    if (!d_hist) return set_err(FK_E_INVALID, "null argument");
-    return spectrum_launch(c, static_cast<uint64_t *>(d_hist), n, static_cast<uint64_t *>(d_tail_kmers));
-}
-
-FK_EXPORT int fk_spectrum(fk_ctx *c, uint64_t *hist, size_t n, uint64_t *tail_kmers) {
-    if (!c) return set_err(FK_E_INVALID, "null ctx");
-    DeviceGuard dg_(c->device);
-    FK_TRY(result_ready(c));
-    if (n < 2) return set_err(FK_E_INVALID, "a spectrum has n >= 2 entries");
-    if (!hist) return set_err(FK_E_INVALID, "null argument");
-    FK_TRY(ensure(c->sp_hist, ((uint64_t)n + 1) * 8));
-    uint64_t *d = c->sp_hist.as<uint64_t>();
-    FK_TRY(spectrum_launch(c, d, n, d + n));
-    HIP_TRY(hipMemcpyAsync(hist, d, (uint64_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-    if (tail_kmers) HIP_TRY(hipMemcpyAsync(tail_kmers, d + n, 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return FK_OK;
-}
-
-// The whole result filtered to [lo, hi]: kept k-mers per bucket -> their scan -> offsets per local bin
-// (d_off on the device, h_off their copy on the host).  kept / off / d_off: the caller's temporaries.
-static int range_offsets(fk_ctx *c, uint32_t lo, uint32_t hi, DevBuf &kept, DevBuf &off, DevBuf &d_off,
-                         std::vector<uint64_t> &h_off) {
-    hipStream_t s = c->stream;
-    const uint64_t nb = c->res_nbuckets;
-    const uint32_t nlb = c->nlb;
-    FK_TRY(ensure(kept, nb * 8));
-    FK_TRY(ensure(off, (nb + 1) * 8));
-    FK_TRY(ensure(d_off, ((uint64_t)nlb + 1) * 8));
-    HIP_TRY(launch_range_count(c->out_counts.as<uint32_t>(), c->buckets.as<Bucket>(), c->dense_off.as<uint64_t>(), nb,
-                               lo, hi, kept.as<uint64_t>(), s));
-    HIP_TRY(scan_excl_sum_u64(kept.as<uint64_t>(), off.as<uint64_t>(), nb, off.as<uint64_t>() + nb, c->ws, s));
-    HIP_TRY(launch_bin_offsets(c->res_fs, off.as<uint64_t>(), nlb, c->res_F, nb, d_off.as<uint64_t>(), s));
-    h_off.assign((size_t)nlb + 1, 0);
-    HIP_TRY(hipMemcpyAsync(h_off.data(), d_off.p, ((uint64_t)nlb + 1) * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return FK_OK;
-}
-
-struct FreeBufs {
-    std::vector<DevBuf *> b;
-    ~FreeBufs() {
-        for (DevBuf *x : b) release(*x);
-    }
-};
-
-FK_EXPORT int fk_bin_sizes_range(fk_ctx *c, uint32_t min_count, uint32_t max_count, uint64_t *out) {
-    if (!c || !out) return set_err(FK_E_INVALID, "null argument");
-    DeviceGuard dg_(c->device);
-    FK_TRY(result_ready(c));
-    FK_TRY(check_count_range(min_count, max_count));
-    for (int32_t b = 0; b < c->Bc; ++b) out[b] = 0;
-    if (c->distinct == 0) return FK_OK;
-    DevBuf kept, off, d_off;
-    FreeBufs guard{{&kept, &off, &d_off}};
-    std::vector<uint64_t> h_off;
-    FK_TRY(range_offsets(c, min_count, max_count, kept, off, d_off, h_off));
-    for (int32_t b = 0; b < c->Bc; ++b)
-        if (owns(c, b)) {
-            const uint32_t lb = local_bin(c, b);
-            out[b] = h_off[lb + 1] - h_off[lb];
-        }
-    return FK_OK;
-}
-
-// One bin filtered: the two range kernels over the bin's buckets [q0, q1) only (gather_bin's).
-FK_EXPORT int fk_get_bin_range(fk_ctx *c, int32_t bin, uint32_t min_count, uint32_t max_count, uint64_t *keys,
-                               uint32_t *counts, size_t cap, size_t *n) {
-    if (!c || !n) return set_err(FK_E_INVALID, "null argument");
-    DeviceGuard dg_(c->device);
-    FK_TRY(result_ready(c));
-    FK_TRY(check_count_range(min_count, max_count));
-    if (bin < 0 || bin >= c->Bc) return set_err(FK_E_RANGE, "bin %d out of [0, %d)", bin, c->Bc);
-    *n = 0;
-    if (!owns(c, bin) || c->distinct == 0) return FK_OK;
-    const uint32_t lb = local_bin(c, bin);
-    if (c->h_bin_off[lb + 1] == c->h_bin_off[lb]) return FK_OK;
-    hipStream_t s = c->stream;
-    uint64_t q[2] = {0, c->res_nbuckets};
-    const uint64_t *fs = c->res_fs;
-    HIP_TRY(hipMemcpyAsync(&q[0], fs + ((uint64_t)lb << c->res_F), 8, hipMemcpyDeviceToHost, s));
-    if (lb + 1 < c->nlb) HIP_TRY(hipMemcpyAsync(&q[1], fs + ((uint64_t)(lb + 1) << c->res_F), 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (q[1] <= q[0] || q[1] > c->res_nbuckets) return FK_OK;
-    const uint64_t nq = q[1] - q[0];
-    FK_TRY(ensure(c->rg_kept, nq * 8));
-    FK_TRY(ensure(c->rg_off, (nq + 1) * 8));
-    const Bucket *bk = c->buckets.as<Bucket>() + q[0];
-    const uint64_t *doff = c->dense_off.as<uint64_t>() + q[0];
-    uint64_t *koff = c->rg_off.as<uint64_t>();
-    HIP_TRY(launch_range_count(c->out_counts.as<uint32_t>(), bk, doff, nq, min_count, max_count,
-                               c->rg_kept.as<uint64_t>(), s));
-    HIP_TRY(scan_excl_sum_u64(c->rg_kept.as<uint64_t>(), koff, nq, koff + nq, c->ws, s));
-    uint64_t cnt = 0;
-    HIP_TRY(hipMemcpyAsync(&cnt, koff + nq, 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    *n = (size_t)cnt;
-    if (cnt == 0) return FK_OK;
-    if (cap < cnt)
-        return set_err(FK_E_RANGE, "bin %d has %llu k-mers with counts in [%u, %u], buffer holds %zu", bin,
-                       (unsigned long long)cnt, min_count, max_count, cap);
-    if (!keys && !counts) return FK_OK;
-    FK_TRY(ensure(c->gather_keys, cnt * 8 * c->KW));
-    FK_TRY(ensure(c->gather_counts, cnt * 4));
-    HIP_TRY(launch_range_compact(c->KW, c->res_keys, c->out_counts.as<uint32_t>(), bk, doff, koff, nq, min_count,
-                                 max_count, c->gather_keys.as<uint64_t>(), c->gather_counts.as<uint32_t>(), s));
-    if (keys) HIP_TRY(hipMemcpyAsync(keys, c->gather_keys.p, cnt * 8 * c->KW, hipMemcpyDeviceToHost, s));
-    if (counts) HIP_TRY(hipMemcpyAsync(counts, c->gather_counts.p, cnt * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return FK_OK;
-}
-
-FK_EXPORT int fk_write_bins_range(fk_ctx *c, const char *out_dir, uint32_t min_count, uint32_t max_count) {
-    if (!c || !out_dir) return set_err(FK_E_INVALID, "null argument");
-    DeviceGuard dg_(c->device);
-    FK_TRY(result_ready(c));
-    FK_TRY(check_count_range(min_count, max_count));
-    if (mkdir_p(out_dir) != 0) return set_err(FK_E_IO, "cannot create %s: %s", out_dir, strerror(errno));
-    if (c->distinct == 0) return FK_OK;  // no k-mers: no bin files
-    DevBuf kept, off, d_off, fkeys, fcounts;
-    FreeBufs guard{{&kept, &off, &d_off, &fkeys, &fcounts}};
-    std::vector<uint64_t> h_off;
-    FK_TRY(range_offsets(c, min_count, max_count, kept, off, d_off, h_off));
-    const uint64_t D = h_off[c->nlb];
-    if (D == 0) return FK_OK;  // nothing kept: no bin files
-    FK_TRY(ensure(fkeys, D * 8 * c->KW));
-    FK_TRY(ensure(fcounts, D * 4));
-    HIP_TRY(launch_range_compact(c->KW, c->res_keys, c->out_counts.as<uint32_t>(), c->buckets.as<Bucket>(),
-                                 c->dense_off.as<uint64_t>(), off.as<uint64_t>(), c->res_nbuckets, min_count,
-                                 max_count, fkeys.as<uint64_t>(), fcounts.as<uint32_t>(), c->stream));
-    // the writer ends with the stream drained (its text copy), before the temporaries are released
-    return write_bin_text(c, out_dir, fkeys.as<uint64_t>(), fcounts.as<uint32_t>(), D, d_off.as<uint64_t>(), h_off);
-}
-
-// ---------------------------------------------------------------------------
-// two-sample comparison (fk_compare.inc): c's result walked, o's looked up in
-// ---------------------------------------------------------------------------
-
-static int32_t bin_owner(const fk_ctx *c, int32_t b) {
-    return c->custom_owners ? c->h_owner[b] : (int32_t)((uint32_t)b % c->G);
-}
-
-// both contexts count the same k-mers into the same bins of the same rank, and hold a result
-static int compare_pair(const fk_ctx *c, const fk_ctx *o) {
-    if (c->cfg.use_ht || o->cfg.use_ht)
-        return set_err(FK_E_INVALID, "a comparison needs the sorted count (use_ht = 0) on both contexts: a use_ht = 1 "
-                                     "result is in table order");
-    if (c->cfg.k != o->cfg.k) return set_err(FK_E_INVALID, "the contexts differ in k: %d and %d", c->cfg.k, o->cfg.k);
-    if (c->cfg.m != o->cfg.m) return set_err(FK_E_INVALID, "the contexts differ in m: %d and %d", c->cfg.m, o->cfg.m);
-    if (c->Bc != o->Bc) return set_err(FK_E_INVALID, "the contexts differ in their bin count: %d and %d", c->Bc, o->Bc);
-    if (c->G != o->G) return set_err(FK_E_INVALID, "the contexts differ in n_ranks: %u and %u", c->G, o->G);
-    if (c->cfg.rank != o->cfg.rank)
-        return set_err(FK_E_INVALID, "the contexts differ in rank: %d and %d", c->cfg.rank, o->cfg.rank);
-    if (c->device != o->device)
-        return set_err(FK_E_INVALID, "the contexts are on different devices: %d and %d", c->device, o->device);
-    if (c->custom_owners || o->custom_owners)
-        for (int32_t b = 0; b < c->Bc; ++b)
-            if (bin_owner(c, b) != bin_owner(o, b))
-                return set_err(FK_E_INVALID, "the contexts differ in their bin owners: bin %d belongs to rank %d and to rank %d",
-                               b, bin_owner(c, b), bin_owner(o, b));
-    if (!c->have_result || !o->have_result)
-        return set_err(FK_E_STATE, "no result on %s: call fk_finish or fk_reduce first",
-                       !c->have_result ? "the walked context" : "the other context");
-    return FK_OK;
-}
-
-// a context's result as the comparison kernels read it; an empty job: no bucket to walk, every lookup 0
-static int compare_tables(fk_ctx *c, QueryTables &t) {
-    if (c->distinct) return query_tables(c, t);
-    t = QueryTables{};
-    t.fm = c->fm;
-    t.G = 1;
-    t.k = c->cfg.k;
-    t.m = c->cfg.m;
-    return FK_OK;
-}
-
-// c's stream waits for everything queued on o's: o's result arrays are complete when c's kernels read them
-static int compare_order(fk_ctx *c, fk_ctx *o) {
-    if (o == c || o->stream == c->stream) return FK_OK;
-    HIP_TRY(hipEventRecord(o->cmp_ev, o->stream));
-    HIP_TRY(hipStreamWaitEvent(c->stream, o->cmp_ev, 0));
-    return FK_OK;
-}
-
-static int check_matrix_shape(size_t rows, size_t cols) {
-    if (rows < 2 || cols < 2 || rows > 65536 || cols > 65536 || (uint64_t)rows * cols > (1ull << 24))
-        return set_err(FK_E_INVALID, "a comparison matrix has 2 <= rows, cols <= 65536 and rows * cols <= 2^24 (got %zu x %zu)",
-                       rows, cols);
-    return FK_OK;
-}
-
-static uint64_t walk_width(const fk_ctx *c) { return c->spectrum_wide ? ~0ull : c->distinct; }
-
-static int compare_launch(fk_ctx *c, fk_ctx *o, uint64_t *d_matrix, size_t rows, size_t cols) {
-    QueryTables ta, tb;
-    FK_TRY(compare_tables(c, ta));
-    FK_TRY(compare_tables(o, tb));
-    FK_TRY(compare_order(c, o));
-    HIP_TRY(launch_compare(c->KW, ta, tb, walk_width(c), d_matrix, (uint32_t)rows, (uint32_t)cols, false, c->stream));
-    // the k-mers only o holds (every k-mer of c's own result is found in it: nothing to add)
-    if (o != c)
-        HIP_TRY(launch_compare(c->KW, tb, ta, walk_width(o), d_matrix, (uint32_t)rows, (uint32_t)cols, true, c->stream));
-    return FK_OK;
-}
-
-FK_EXPORT int fk_compare_device(fk_ctx *c, fk_ctx *o, void *d_matrix, size_t rows, size_t cols) {
-    if (!c || !o) return set_err(FK_E_INVALID, "null ctx");
-    DeviceGuard dg_(c->device);
-    FK_TRY(check_matrix_shape(rows, cols));
-    FK_TRY(compare_pair(c, o));
-    if (!d_matrix) return set_err(FK_E_INVALID, "null argument");
-    return compare_launch(c, o, static_cast<uint64_t *>(d_matrix), rows, cols);
-}
-
-FK_EXPORT int fk_compare(fk_ctx *c, fk_ctx *o, uint64_t *matrix, size_t rows, size_t cols) {
-    if (!c || !o) return set_err(FK_E_INVALID, "null ctx");
-    DeviceGuard dg_(c->device);
-    FK_TRY(check_matrix_shape(rows, cols));
-    FK_TRY(compare_pair(c, o));
-    if (!matrix) return set_err(FK_E_INVALID, "null argument");
-    const uint64_t bytes = (uint64_t)rows * cols * 8;
-    FK_TRY(ensure(c->cmp_mat, bytes));
-    FK_TRY(compare_launch(c, o, c->cmp_mat.as<uint64_t>(), rows, cols));
-    HIP_TRY(hipMemcpyAsync(matrix, c->cmp_mat.p, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return FK_OK;
-}
-
-static int check_join_range(uint32_t lo, uint32_t hi, uint32_t olo, uint32_t ohi) {
-    FK_TRY(check_count_range(lo, hi));
-    if (olo > ohi) return set_err(FK_E_INVALID, "other_min %u > other_max %u", olo, ohi);
-    return FK_OK;
-}
-
-FK_EXPORT int fk_bin_sizes_joined(fk_ctx *c, fk_ctx *o, uint32_t min_count, uint32_t max_count, uint32_t other_min,
-                                  uint32_t other_max, uint64_t *out) {
-    if (!c || !o || !out) return set_err(FK_E_INVALID, "null argument");
-    DeviceGuard dg_(c->device);
-    FK_TRY(compare_pair(c, o));
-    FK_TRY(check_join_range(min_count, max_count, other_min, other_max));
-    for (int32_t b = 0; b < c->Bc; ++b) out[b] = 0;
-    if (c->distinct == 0) return FK_OK;
-    QueryTables ta, tb;
-    FK_TRY(compare_tables(c, ta));
-    FK_TRY(compare_tables(o, tb));
-    FK_TRY(compare_order(c, o));
-    // range_offsets with the joined predicate: kept per bucket -> scan -> offsets per local bin
-    DevBuf kept, off, d_off;
-    FreeBufs guard{{&kept, &off, &d_off}};
-    hipStream_t s = c->stream;
-    const uint64_t nb = c->res_nbuckets;
-    const uint32_t nlb = c->nlb;
-    FK_TRY(ensure(kept, nb * 8));
-    FK_TRY(ensure(off, (nb + 1) * 8));
-    FK_TRY(ensure(d_off, ((uint64_t)nlb + 1) * 8));
-    HIP_TRY(launch_join_count(c->KW, ta, tb, min_count, max_count, other_min, other_max, kept.as<uint64_t>(), s));
-    HIP_TRY(scan_excl_sum_u64(kept.as<uint64_t>(), off.as<uint64_t>(), nb, off.as<uint64_t>() + nb, c->ws, s));
-    HIP_TRY(launch_bin_offsets(c->res_fs, off.as<uint64_t>(), nlb, c->res_F, nb, d_off.as<uint64_t>(), s));
-    std::vector<uint64_t> h_off((size_t)nlb + 1, 0);
-    HIP_TRY(hipMemcpyAsync(h_off.data(), d_off.p, ((uint64_t)nlb + 1) * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    for (int32_t b = 0; b < c->Bc; ++b)
-        if (owns(c, b)) {
-            const uint32_t lb = local_bin(c, b);
-            out[b] = h_off[lb + 1] - h_off[lb];
-        }
-    return FK_OK;
-}
-
-// One bin joined: the two join kernels over the bin's buckets [q0, q1) only, as fk_get_bin_range.
-FK_EXPORT int fk_get_bin_joined(fk_ctx *c, fk_ctx *o, int32_t bin, uint32_t min_count, uint32_t max_count,
-                                uint32_t other_min, uint32_t other_max, uint64_t *keys, uint32_t *counts,
-                                uint32_t *other_counts, size_t cap, size_t *n) {
-    if (!c || !o || !n) return set_err(FK_E_INVALID, "null argument");
-    DeviceGuard dg_(c->device);
-    FK_TRY(compare_pair(c, o));
-    FK_TRY(check_join_range(min_count, max_count, other_min, other_max));
-    if (bin < 0 || bin >= c->Bc) return set_err(FK_E_RANGE, "bin %d out of [0, %d)", bin, c->Bc);
-    *n = 0;
-    if (!owns(c, bin) || c->distinct == 0) return FK_OK;
-    const uint32_t lb = local_bin(c, bin);
-    if (c->h_bin_off[lb + 1] == c->h_bin_off[lb]) return FK_OK;
-    QueryTables ta, tb;
-    FK_TRY(compare_tables(c, ta));
-    FK_TRY(compare_tables(o, tb));
-    FK_TRY(compare_order(c, o));
-    hipStream_t s = c->stream;
-    uint64_t q[2] = {0, c->res_nbuckets};
-    const uint64_t *fs = c->res_fs;
-    HIP_TRY(hipMemcpyAsync(&q[0], fs + ((uint64_t)lb << c->res_F), 8, hipMemcpyDeviceToHost, s));
-    if (lb + 1 < c->nlb) HIP_TRY(hipMemcpyAsync(&q[1], fs + ((uint64_t)(lb + 1) << c->res_F), 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (q[1] <= q[0] || q[1] > c->res_nbuckets) return FK_OK;
-    const uint64_t nq = q[1] - q[0];
-    FK_TRY(ensure(c->rg_kept, nq * 8));
-    FK_TRY(ensure(c->rg_off, (nq + 1) * 8));
-    ta.buckets += q[0];  // the walk covers the bin's buckets only
-    ta.dense_off += q[0];
-    ta.nbuckets = nq;
-    uint64_t *koff = c->rg_off.as<uint64_t>();
-    HIP_TRY(launch_join_count(c->KW, ta, tb, min_count, max_count, other_min, other_max, c->rg_kept.as<uint64_t>(), s));
-    HIP_TRY(scan_excl_sum_u64(c->rg_kept.as<uint64_t>(), koff, nq, koff + nq, c->ws, s));
-    uint64_t cnt = 0;
-    HIP_TRY(hipMemcpyAsync(&cnt, koff + nq, 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    *n = (size_t)cnt;
-    if (cnt == 0) return FK_OK;
-    if (cap < cnt)
-        return set_err(FK_E_RANGE, "bin %d has %llu k-mers with counts in [%u, %u] and [%u, %u] in the other result, buffer holds %zu",
-                       bin, (unsigned long long)cnt, min_count, max_count, other_min, other_max, cap);
-    if (!keys && !counts && !other_counts) return FK_OK;
-    FK_TRY(ensure(c->gather_keys, cnt * 8 * c->KW));
-    FK_TRY(ensure(c->gather_counts, cnt * 4));
-    FK_TRY(ensure(c->gather_other, cnt * 4));
-    HIP_TRY(launch_join_compact(c->KW, ta, tb, min_count, max_count, other_min, other_max, koff,
-                                c->gather_keys.as<uint64_t>(), c->gather_counts.as<uint32_t>(),
-                                c->gather_other.as<uint32_t>(), s));
-    if (keys) HIP_TRY(hipMemcpyAsync(keys, c->gather_keys.p, cnt * 8 * c->KW, hipMemcpyDeviceToHost, s));
-    if (counts) HIP_TRY(hipMemcpyAsync(counts, c->gather_counts.p, cnt * 4, hipMemcpyDeviceToHost, s));
-    if (other_counts) HIP_TRY(hipMemcpyAsync(other_counts, c->gather_other.p, cnt * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return FK_OK;
-}
-
-// ---------------------------------------------------------------------------
-// per-read abundance profiles of the counted result (fk_reads.inc)
-// ---------------------------------------------------------------------------
-
-static_assert(FK_READ_TILE == READ_TILE, "fastkmer.h names the kernel's tile");
-static_assert(sizeof(fk_read_stat) == 32 && sizeof(ReadStat) == 32, "fk_read_stat is 32 bytes");
-
-// Host only: FASTA / FASTQ text cut into a CSR read batch, the reads as the count sees them.
-namespace {
-struct CsrOut {
-    uint8_t *bases;
-    size_t cap_bases;
-    uint64_t *offsets;
-    size_t cap_reads;
-    size_t nr = 0, nb = 0;
-    bool fill, over = false;
-    void begin_read() {
-        if (fill) {
-            if (nr < cap_reads)
-                offsets[nr] = nb;
-            else
-                over = true;
-        }
-        ++nr;
-    }
-    void append(const uint8_t *p, size_t len) {
-        if (fill) {
-            if (nb + len <= cap_bases)
-                memcpy(bases + nb, p, len);
-            else
-                over = true;
-        }
-        nb += len;
-    }
-};
-}  // namespace
-
-FK_EXPORT int fk_reads_csr(const uint8_t *text, size_t n, int32_t format, int32_t min_quality, int32_t quality_offset,
-                           uint8_t *bases, size_t cap_bases, uint64_t *offsets, size_t cap_reads, size_t *n_reads,
-                           size_t *n_bases) {
-    if ((!text && n) || !n_reads || !n_bases) return set_err(FK_E_INVALID, "null argument");
-    *n_reads = 0;
-    *n_bases = 0;
-    if (format != FK_FORMAT_FASTA && format != FK_FORMAT_FASTQ) return set_err(FK_E_INVALID, "unknown input format %d", format);
-    if (quality_offset != 33 && quality_offset != 64)
-        return set_err(FK_E_INVALID, "quality_offset must be 33 or 64, got %d", quality_offset);
-    if (min_quality < 0 || min_quality > 93) return set_err(FK_E_INVALID, "min_quality must be in 0..93, got %d", min_quality);
-    CsrOut o{bases, cap_bases, offsets, cap_reads};
-    o.fill = bases && offsets;
-    uint64_t bad = UINT64_MAX;
-    if (format == FK_FORMAT_FASTA) {
-        // the parse's grammar (fk_parse.inc, oracle for_each_read): a non-empty line beginning with '>' is a
-        // header, the lines up to the next header are its read without their '\n', lines before the first
-        // header are no sequence
-        bool in_record = false;
-        for (size_t pos = 0; pos < n;) {
-            const uint8_t *nl = static_cast<const uint8_t *>(memchr(text + pos, '\n', n - pos));
-            const size_t e = nl ? (size_t)(nl - text) : n;
-            if (e > pos && text[pos] == '>') {
-                in_record = true;
-                o.begin_read();
-            } else if (in_record) {
-                o.append(text + pos, e - pos);
-            }
-            pos = e + 1;
-        }
-    } else {
-        // fk_fastq.inc's grammar: the lines up to the last one holding a byte other than '\n' / '\r', rounded
-        // up to whole records of four where blank lines follow; a trailing '\r' is outside the two lengths
-        std::vector<size_t> ls;  // line starts, then n + 1 (every line ends one before the next start)
-        for (size_t pos = 0; pos < n;) {
-            ls.push_back(pos);
-            const uint8_t *nl = static_cast<const uint8_t *>(memchr(text + pos, '\n', n - pos));
-            pos = nl ? (size_t)(nl - text) + 1 : n + 1;
-        }
-        const size_t nlines = ls.size();
-        ls.push_back(n && text[n - 1] == '\n' ? n : n + 1);
-        size_t ntext = 0;  // lines up to the last one with text
-        for (size_t i = nlines; i-- > 0 && !ntext;)
-            for (size_t q = ls[i]; q + 1 < ls[i + 1]; ++q)
-                if (text[q] != '\r') {
-                    ntext = i + 1;
-                    break;
-                }
-        const size_t neff = std::min(nlines, (ntext + 3) & ~(size_t)3), nrec = neff / 4;
-        if (neff & 3) bad = nrec;
-        for (size_t r = 0; r < nrec && r < bad; ++r) {
-            const size_t s0 = ls[4 * r], e0 = ls[4 * r + 1] - 1, s1 = ls[4 * r + 1], e1 = ls[4 * r + 2] - 1;
-            const size_t s2 = ls[4 * r + 2], e2 = ls[4 * r + 3] - 1, s3 = ls[4 * r + 3], e3 = std::min(ls[4 * r + 4] - 1, n);
-            size_t len1 = e1 - s1, len3 = e3 - s3;
-            if (len1 && text[e1 - 1] == '\r') --len1;
-            if (len3 && text[e3 - 1] == '\r') --len3;
-            if (!(e0 > s0 && text[s0] == '@' && e2 > s2 && text[s2] == '+' && len1 == len3)) {
-                bad = r;
-                break;
-            }
-            o.begin_read();
-            const size_t at = o.nb;
-            o.append(text + s1, e1 - s1);
-            if (o.fill && !o.over && min_quality > 0)
-                for (size_t j = 0; j < len1; ++j)
-                    if ((int)text[s3 + j] - quality_offset < min_quality) bases[at + j] = 'N';
-        }
-    }
-    if (o.fill) {
-        if (o.nr <= cap_reads)
-            offsets[o.nr] = o.nb;
-        else
-            o.over = true;
-    }
-    *n_reads = o.nr;
-    *n_bases = o.nb;
-    if (bad != UINT64_MAX)
-        return set_err(FK_E_INVALID, "FASTQ record %llu is malformed (no '@' or '+' line, quality and sequence of "
-                                     "different lengths, or the input ends inside it)", (unsigned long long)bad);
-    if (o.over)
-        return set_err(FK_E_RANGE, "the text holds %zu reads of %zu bases, the buffers hold %zu and %zu", o.nr, o.nb,
-                       cap_reads, cap_bases);
-    return FK_OK;
-}
-
-FK_EXPORT size_t fk_read_stats_scratch_bytes(size_t n_bases) { return 5 * n_bases; }
-
-// offsets[0] == 0 and ascending (host forms)
-static int check_offsets(const uint64_t *offsets, size_t n_reads) {
-    if (offsets[0] != 0) return set_err(FK_E_INVALID, "offsets[0] is %llu, not 0", (unsigned long long)offsets[0]);
-    for (size_t i = 0; i < n_reads; ++i)
-        if (offsets[i + 1] < offsets[i])
-            return set_err(FK_E_INVALID, "offsets do not ascend at read %zu (%llu after %llu)", i,
-                           (unsigned long long)offsets[i + 1], (unsigned long long)offsets[i]);
-    return FK_OK;
-}
-
-static int need_all_counts(const fk_ctx *c, const char *what) {
-    if (c->cfg.n_ranks > 1)
-        return set_err(FK_E_INVALID, "%s needs every k-mer's count and this context is rank %d of %d: sum the ranks' "
-                                     "fk_read_counts arrays and reduce them with fk_read_stats_of_counts_device",
-                       what, c->cfg.rank, c->cfg.n_ranks);
-    return FK_OK;
-}
-
-FK_EXPORT int fk_read_counts_device(fk_ctx *c, const void *d_bases, const void *d_offsets, size_t n_reads,
-                                    void *d_counts, void *d_valid) {
-    if (!c) return set_err(FK_E_INVALID, "null ctx");
-    DeviceGuard dg_(c->device);
-    QueryTables t;
-    FK_TRY(query_tables(c, t));
-    if (n_reads == 0) return FK_OK;
-    if (!d_bases || !d_offsets || !d_counts) return set_err(FK_E_INVALID, "null argument");
-    HIP_TRY(launch_read_counts(c->KW, t, static_cast<const uint8_t *>(d_bases), static_cast<const uint64_t *>(d_offsets),
-                               n_reads, 0, UINT64_MAX, static_cast<uint32_t *>(d_counts),
-                               static_cast<uint8_t *>(d_valid), c->stream));
-    return FK_OK;
-}
-
-FK_EXPORT int fk_read_counts(fk_ctx *c, const uint8_t *bases, const uint64_t *offsets, size_t n_reads,
-                             uint32_t *counts, uint8_t *valid) {
-    if (!c) return set_err(FK_E_INVALID, "null ctx");
-    DeviceGuard dg_(c->device);
-    QueryTables t;
-    FK_TRY(query_tables(c, t));
-    if (!offsets) return set_err(FK_E_INVALID, "null argument");
-    FK_TRY(check_offsets(offsets, n_reads));
-    const size_t n = (size_t)offsets[n_reads], k = (size_t)c->cfg.k;
-    if (n == 0) return FK_OK;
-    if (!bases || !counts) return set_err(FK_E_INVALID, "null argument");
-    hipStream_t s = c->stream;
-    // positions [at, at + nc) read the bases [at, at + nc + k - 1) and the offsets of the reads that touch them,
-    // rebased: the first read cut at `at`, the last at the end of the halo
-    const size_t chunk = (size_t)std::min<uint64_t>(query_chunk(), n);
-    FK_TRY(ensure(c->q_in, chunk + k));
-    FK_TRY(ensure(c->q_counts, (chunk + k) * 4));
-    if (valid) FK_TRY(ensure(c->rd_valid, chunk + k));
-    std::vector<uint64_t> sub;
-    const uint64_t *const oend = offsets + n_reads + 1;
-    for (size_t at = 0; at < n; at += chunk) {
-        const size_t nc = std::min(chunk, n - at), len = std::min(nc + k - 1, n - at);
-        const uint64_t *i0 = std::upper_bound(offsets, oend, (uint64_t)at) - 1;  // the last read beginning at or before
-        const uint64_t *i1 = std::lower_bound(i0 + 1, oend, (uint64_t)(at + len));
-        const size_t nsub = (size_t)(i1 - i0);
-        sub.assign(nsub + 1, 0);
-        for (size_t j = 1; j < nsub; ++j) sub[j] = i0[j] - at;
-        sub[nsub] = len;
-        FK_TRY(ensure(c->rd_off, (nsub + 1) * 8));
-        HIP_TRY(hipMemcpyAsync(c->q_in.p, bases + at, len, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(c->rd_off.p, sub.data(), (nsub + 1) * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(launch_read_counts(c->KW, t, c->q_in.as<uint8_t>(), c->rd_off.as<uint64_t>(), nsub, len, len,
-                                   c->q_counts.as<uint32_t>(), valid ? c->rd_valid.as<uint8_t>() : nullptr, s));
-        HIP_TRY(hipMemcpyAsync(counts + at, c->q_counts.p, nc * 4, hipMemcpyDeviceToHost, s));
-        if (valid) HIP_TRY(hipMemcpyAsync(valid + at, c->rd_valid.p, nc, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));  // the staging buffers are free for the next chunk
-    }
-    return FK_OK;
-}
-
-FK_EXPORT int fk_read_stats_of_counts_device(fk_ctx *c, const void *d_counts, const void *d_valid, const void *d_offsets,
-                                             size_t n_reads, uint32_t min_count, uint32_t max_count, void *d_stats) {
-    if (!c) return set_err(FK_E_INVALID, "null ctx");
-    DeviceGuard dg_(c->device);
-    FK_TRY(check_count_range(min_count, max_count));
-    if (n_reads == 0) return FK_OK;
-    if (!d_counts || !d_offsets || !d_stats) return set_err(FK_E_INVALID, "null argument");
-    HIP_TRY(launch_read_stats(static_cast<const uint32_t *>(d_counts), static_cast<const uint8_t *>(d_valid),
-                              static_cast<const uint64_t *>(d_offsets), n_reads, UINT64_MAX, c->cfg.k, min_count,
-                              max_count, static_cast<ReadStat *>(d_stats), c->stream));
-    return FK_OK;
-}
-
-FK_EXPORT int fk_read_stats_device(fk_ctx *c, const void *d_bases, const void *d_offsets, size_t n_reads,
-                                   uint32_t min_count, uint32_t max_count, void *d_scratch, size_t scratch_bytes,
-                                   void *d_stats) {
-    if (!c) return set_err(FK_E_INVALID, "null ctx");
-    DeviceGuard dg_(c->device);
-    FK_TRY(need_all_counts(c, "fk_read_stats_device"));
-    QueryTables t;
-    FK_TRY(query_tables(c, t));
-    FK_TRY(check_count_range(min_count, max_count));
-    if (n_reads == 0) return FK_OK;
-    if (!d_bases || !d_offsets || !d_stats || (!d_scratch && scratch_bytes)) return set_err(FK_E_INVALID, "null argument");
-    if (reinterpret_cast<uintptr_t>(d_scratch) & 3) return set_err(FK_E_INVALID, "d_scratch must be 4-byte aligned");
-    // the scratch holds uint32 counts then uint8 valid flags of `cap` positions; the kernels stop at cap
-    const uint64_t cap = scratch_bytes / 5;
-    uint32_t *cnt = static_cast<uint32_t *>(d_scratch);
-    uint8_t *val = static_cast<uint8_t *>(d_scratch) + 4 * cap;
-    if (cap)
-        HIP_TRY(launch_read_counts(c->KW, t, static_cast<const uint8_t *>(d_bases),
-                                   static_cast<const uint64_t *>(d_offsets), n_reads, cap, cap, cnt, val, c->stream));
-    HIP_TRY(launch_read_stats(cnt, val, static_cast<const uint64_t *>(d_offsets), n_reads, cap, c->cfg.k, min_count,
-                              max_count, static_cast<ReadStat *>(d_stats), c->stream));
-    return FK_OK;
-}
-
-FK_EXPORT int fk_read_stats(fk_ctx *c, const uint8_t *bases, const uint64_t *offsets, size_t n_reads,
-                            uint32_t min_count, uint32_t max_count, fk_read_stat *stats) {
-    if (!c) return set_err(FK_E_INVALID, "null ctx");
-    DeviceGuard dg_(c->device);
-    FK_TRY(need_all_counts(c, "fk_read_stats"));
-    QueryTables t;
-    FK_TRY(query_tables(c, t));
-    FK_TRY(check_count_range(min_count, max_count));
-    if (!offsets) return set_err(FK_E_INVALID, "null argument");
-    FK_TRY(check_offsets(offsets, n_reads));
-    if (n_reads == 0) return FK_OK;
-    if ((!bases && offsets[n_reads]) || !stats) return set_err(FK_E_INVALID, "null argument");
-    hipStream_t s = c->stream;
-    // whole reads per chunk: as many as fit FASTKMER_QUERY_CHUNK positions (and as many reads), at least one
-    const uint64_t chunk = query_chunk();
-    std::vector<uint64_t> sub;
-    for (size_t r0 = 0; r0 < n_reads;) {
-        size_t r1 = r0 + 1;
-        while (r1 < n_reads && offsets[r1 + 1] - offsets[r0] <= chunk && r1 - r0 < chunk) ++r1;
-        const size_t nr = r1 - r0, len = (size_t)(offsets[r1] - offsets[r0]);
-        sub.resize(nr + 1);
-        for (size_t j = 0; j <= nr; ++j) sub[j] = offsets[r0 + j] - offsets[r0];
-        FK_TRY(ensure(c->q_in, len));
-        FK_TRY(ensure(c->q_counts, len * 4));
-        FK_TRY(ensure(c->rd_valid, len));
-        FK_TRY(ensure(c->rd_off, (nr + 1) * 8));
-        FK_TRY(ensure(c->rd_stats, nr * sizeof(ReadStat)));
-        if (len) HIP_TRY(hipMemcpyAsync(c->q_in.p, bases + offsets[r0], len, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(c->rd_off.p, sub.data(), (nr + 1) * 8, hipMemcpyHostToDevice, s));
-        if (len)
-            HIP_TRY(launch_read_counts(c->KW, t, c->q_in.as<uint8_t>(), c->rd_off.as<uint64_t>(), nr, len, len,
-                                       c->q_counts.as<uint32_t>(), c->rd_valid.as<uint8_t>(), s));
-        HIP_TRY(launch_read_stats(c->q_counts.as<uint32_t>(), c->rd_valid.as<uint8_t>(), c->rd_off.as<uint64_t>(), nr,
-                                  len, c->cfg.k, min_count, max_count, c->rd_stats.as<ReadStat>(), s));
-        HIP_TRY(hipMemcpyAsync(stats + r0, c->rd_stats.p, nr * sizeof(ReadStat), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        r0 = r1;
-    }
     return FK_OK;
 }
 
@@ -4468,13 +3206,7 @@ FK_EXPORT int fk_write_bin_signatures(fk_ctx *c, const void *d_counts, uint64_t 
                        (unsigned long long)n_counts, (unsigned long long)slots);
     hipStream_t s = c->stream;
     const unsigned long long *counts = (const unsigned long long *)d_counts;
-    DevBuf nz, pairs;
-    struct Free {
-        DevBuf *b[2];
-        ~Free() {
-            for (DevBuf *x : b) release(*x);
-        }
-    } guard{{&nz, &pairs}};
+    TempBuf nz, pairs;
     FK_TRY(ensure(nz, 8));
     unsigned long long nnz = 0;
     HIP_TRY(hipMemsetAsync(nz.p, 0, 8, s));
@@ -4531,11 +3263,7 @@ FK_EXPORT int fk_find_bin_signatures(fk_ctx *c, const char *out_dir) {
     if (!c || !out_dir) return set_err(FK_E_INVALID, "null argument");
     DeviceGuard dg_(c->device);
     const uint64_t slots = fk_signature_slots(c);
-    DevBuf counts;
-    struct Free {
-        DevBuf *b;
-        ~Free() { release(*b); }
-    } guard{&counts};
+    TempBuf counts;
     FK_TRY(ensure(counts, slots * 8));
     FK_TRY(fk_signature_counts(c, counts.p, slots));
     return fk_write_bin_signatures(c, counts.p, slots, out_dir);

@@ -1,0 +1,391 @@
+// fk_ctx.h -- private: the context behind the C-ABI's fk_ctx and the host helpers shared by fk_api.cpp (the
+// context, the input and the count) and fk_views.cpp (the calls that only read a finished result).  Both are
+// compiled with the same -D flags (fk_ctx has FK_PROBES members).
+#pragma once
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "../../include/fastkmer.h"
+#include "fk_comm.h"
+#include "fk_internal.h"
+
+#define FK_EXPORT extern "C" __attribute__((visibility("default")))
+
+namespace fk {
+int set_err(int code, const char *fmt, ...);  // fk_api.cpp: the calling thread's fk_last_error message; returns code
+int mkdir_p(const std::string &path);         // fk_views.cpp
+
+#define HIP_TRY(expr)                                                                                \
+    do {                                                                                             \
+        hipError_t e_ = (expr);                                                                      \
+        if (e_ != hipSuccess)                                                                        \
+            return set_err(e_ == hipErrorOutOfMemory ? FK_E_NOMEM : FK_E_DEVICE, "%s failed: %s (%s:%d)", \
+                           #expr, hipGetErrorString(e_), __FILE__, __LINE__);                        \
+    } while (0)
+
+#define FK_TRY(expr)             \
+    do {                         \
+        int r_ = (expr);         \
+        if (r_ != FK_OK) return r_; \
+    } while (0)
+
+// Grow-only pinned host memory: small uploads and read-backs on the hot path go
+// through it (pageable transfers are staged by the runtime, and block the host).
+struct PinBuf {
+    void *p = nullptr;
+    size_t bytes = 0;
+    int ensure(size_t need) {
+        if (bytes >= need) return FK_OK;
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        bytes = 0;
+        const size_t want = std::max<size_t>(need + need / 4, 4096);
+        if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            return FK_E_NOMEM;
+        }
+        bytes = want;
+        return FK_OK;
+    }
+    void release() {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
+    template <typename T>
+    T *as() const { return reinterpret_cast<T *>(p); }
+};
+
+struct DevBuf {
+    void *p = nullptr;
+    size_t bytes = 0;
+    template <typename T>
+    T *as() const { return reinterpret_cast<T *>(p); }
+};
+
+inline int ensure(DevBuf &b, size_t bytes) {
+    if (bytes == 0) bytes = 16;
+    if (b.bytes >= bytes) return FK_OK;
+    if (b.p) (void)hipFree(b.p);
+    b.p = nullptr;
+    b.bytes = 0;
+    // slack for the next job's slightly larger input: an eighth, at most 1 GiB (4 GB of slack on each
+    // k-mer array of a 6.25 GB job would cost more HBM than the reallocations it saves)
+    const size_t want = bytes + std::min<size_t>(bytes / 8, 1ull << 30) + 256;
+    hipError_t e = hipMalloc(&b.p, want);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return set_err(FK_E_NOMEM, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
+    }
+    b.bytes = want;
+    return FK_OK;
+}
+
+inline void release(DevBuf &b) {
+    if (b.p) (void)hipFree(b.p);
+    b.p = nullptr;
+    b.bytes = 0;
+}
+
+// A call's own temporary, released when its scope ends; the call drains the stream that reads it before.
+struct TempBuf : DevBuf {
+    TempBuf() = default;
+    ~TempBuf() { release(*this); }
+    TempBuf(const TempBuf &) = delete;
+    TempBuf &operator=(const TempBuf &) = delete;
+};
+
+// Record partition (fk_partition.inc): histogram -> scan -> scatter.
+struct PartBufs {
+    DevBuf H, K, Hs, Ts, KT;              // per-workgroup histograms and destinations (rows), segment sums
+    DevBuf rec, kmer, off, cursor;        // per-part totals / offsets (device), cursor: global path only
+    uint32_t nparts = 0;
+    RecSrc src{};                         // the records counted (part_scatter reads the same)
+    bool global = false;                  // nparts > PART_MAX: global-atomic kernels
+    void release_all() {
+        for (DevBuf *b : {&H, &K, &Hs, &Ts, &KT, &rec, &kmer, &off, &cursor}) release(*b);
+    }
+};
+
+inline int32_t clamp_bins(int32_t m, int32_t B) {
+    // test/package.scala:32: Math.min(Math.pow(4, m), max_b).toInt
+    double p = 1.0;
+    for (int i = 0; i < m; ++i) p *= 4.0;
+    const double b = p < (double)B ? p : (double)B;
+    return (int32_t)b;
+}
+
+// Every exported call that touches the GPU selects the context's device for
+// its duration and restores the caller's current device on return, so one
+// thread may drive contexts on several GPUs and a context may move between
+// threads (e.g. JNI executor threads).
+struct DeviceGuard {
+    int prev = -1;
+    explicit DeviceGuard(int dev) {
+        if (hipGetDevice(&prev) != hipSuccess) {
+            (void)hipGetLastError();
+            prev = -1;
+        }
+        if (dev >= 0 && prev != dev) {
+            (void)hipSetDevice(dev);
+        } else {
+            prev = -1;  // nothing to restore
+        }
+    }
+    ~DeviceGuard() {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+    DeviceGuard(const DeviceGuard &) = delete;
+    DeviceGuard &operator=(const DeviceGuard &) = delete;
+};
+
+// The sorted count's shape: cell bits F (super-cells of 2^F2 cells), tiers.
+struct SortedPlan {
+    int F = 1, F2 = 0, F1 = 1;
+    bool tiered = false, two_level = false;
+    uint32_t cap = 2048, wave_cap = WAVE_BUCKET_CAP;
+    uint64_t max_bin = 0;  // the largest bin's k-mers the plan was made for
+};
+
+// A stream and the scan workspace its scans use.  The count's stages take one as a parameter: the
+// context's own (`stream`, `ws`) or the staging stream's (`xstage`, `ws_x`); see main_on / stage_on.
+// A scan owns its workspace from launch to completion, so two streams share one only while their
+// scans are ordered by events.  The side stream (`tier_side`) borrows the main stream's workspace
+// under this rule: its scans (the last piece's bucket cut, the split's sizes) are queued behind a wait
+// for an event recorded on the main stream after that stream's last scan (side_ev[2] after the
+// cell-offset scan of the last piece, or side_ev[3] behind the cut), and the main stream queues no scan
+// again until it has waited for the side stream's work (side_ev[0] after the cut, side_ev[1] after the
+// heavy tiers: the result's scans follow it).
+struct StreamWs {
+    hipStream_t s;
+    ScanWorkspace *ws;
+};
+
+// The result views' staging (fk_views.cpp): grow-only, reused from call to call.
+struct ViewBufs {
+    DevBuf gather_keys, gather_counts, gather_other;  // one bin gathered or filtered (other: its counts in the other result)
+    DevBuf q_in, q_counts, q_bins;      // fk_query / fk_query_sequence: one chunk's keys (or bases), counts and bins
+    DevBuf rd_off, rd_valid, rd_stats;  // fk_read_counts / _stats: one chunk's offsets, valid flags, statistics (bases in q_in)
+    DevBuf sp_hist, cmp_mat;            // fk_spectrum: the histogram and its tail sum; fk_compare: the matrix
+    DevBuf rg_kept, rg_off;             // a filtered bin: kept k-mers per bucket of the bin and their scan
+    void release_all() {
+        for (DevBuf *b : {&gather_keys, &gather_counts, &gather_other, &q_in, &q_counts, &q_bins, &rd_off, &rd_valid,
+                          &rd_stats, &sp_hist, &rg_kept, &rg_off, &cmp_mat})
+            release(*b);
+    }
+};
+
+}  // namespace fk
+using namespace fk;
+
+struct fk_ctx {
+    fk_config cfg{};
+    int32_t Bc = 0;    // b = min(4^m, B)
+    uint32_t G = 1;    // ranks
+    uint32_t nlb = 0;  // local bins: b = rank + G * lb (default placement) or lbin_bin[lb] (custom)
+    // size-aware placement (fk_set_bin_owners): bin -> rank, bin -> local index, local index -> bin
+    bool custom_owners = false;
+    std::vector<int32_t> h_owner, h_lbin_bin;
+    std::vector<uint32_t> h_bin_lbin;
+    DevBuf d_owner, d_local;  // REC_BIN_MASK + 1 entries each (~0u: no part), device copies of the above
+    int W = 2, KW = 1;
+    FastMod fm{};
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    // Test hooks (result-preserving; they steer inputs that FASTA data cannot aim at onto a path):
+    bool force_large = false;  // FASTKMER_DEBUG_LARGE_BUCKETS=1: route every bucket through the streaming path
+    uint32_t cell_target = 0;  // FASTKMER_DEBUG_CELL_TARGET: average keys per cell of the largest bin (0: auto)
+    int mid_parts = -1;        // FASTKMER_DEBUG_MID_PARTS: the 64-bit mid tier's key ranges always (1), the whole
+                               // buckets on the 512-key table always (2), the 1024-key kernel only (0), by size (-1)
+    bool split_retry = false;  // FASTKMER_DEBUG_SPLIT_RETRY: every split bucket cut a second time
+    bool spectrum_wide = false;  // FASTKMER_DEBUG_SPECTRUM_WIDE: the spectrum kernel of results of >= 2^32 k-mers
+    int x2_l1 = 0;             // FASTKMER_X2_L1: level-1 workgroup size (512, 1024; 0 = by fan-out)
+    int fused = 1;             // FASTKMER_FUSED=0: two-kernel map (parse, then signature) for every input
+#ifdef FK_PROBES
+    // Measurement-only (a library built with -DFK_PROBES; wrong results by design):
+    int dbg_phase = 99;        // FASTKMER_DEBUG_PHASE: stop the bucket kernel early
+    int fused_probe = 0;       // FASTKMER_FUSED_PROBE: stop the fused map kernel after a phase
+    int split_map = 0;         // FASTKMER_SPLIT_MAP=1: the map as a parse kernel + a signature-pass kernel
+#endif
+    bool last_map_fused = false;  // the last fk_map used the fused kernel (stats, tests)
+    // grouped emit (fk_set_grouped_emit): send buffer grouped by (destination, local bin)
+    bool grouped = false;
+    uint32_t grp_nlb = 0;                    // parts per destination = ceil(Bc / n_ranks)
+    DevBuf grp_table;                        // bin -> dest * grp_nlb + bin / n_ranks
+    std::vector<uint64_t> grp_rec, grp_kmer; // per part, after fk_map
+    const uint64_t *rsrc = nullptr;          // records the count stage reads (precs, or d_recv when grouped)
+
+    // input
+    // host ingest: bytes are streamed to fasta_own (appended until the next fk_map)
+    bool ingest_fresh = true;        // the next fk_ingest starts a new input
+    bool dev_open = false;           // fk_ingest_device(..., last = 0): the borrowed input is unfinished
+    void *pinned[2] = {nullptr, nullptr};  // staging for pageable sources
+    hipEvent_t pin_ev[2] = {nullptr, nullptr};
+    hipStream_t copy_stream = nullptr;     // H2D of fk_ingest (the map runs on `stream` meanwhile)
+    hipStream_t tier_side = nullptr;       // the count's heavy tiers beside the wave tier, the last piece's cut
+    // [0] cut -> wave tier, [1] heavy tiers -> result, [2] last piece's cell offsets -> cut, [3] -> heavy
+    hipEvent_t side_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t seg_ev = nullptr;           // "segment landed" (copy stream -> map stream)
+    hipEvent_t h2d_ev[2] = {nullptr, nullptr};  // first copy issued / last copy done (timing)
+    // streamed map (fused path): fk_ingest maps every tile whose bytes (and halo) have landed
+    bool pm_active = false;     // the current input is being mapped while it is copied
+    uint64_t pm_tiles = 0;      // tiles [0, pm_tiles) launched
+    bool pm_last_seen = false;  // an fk_ingest with last = 1 launched the final tiles
+    const uint8_t *d_fasta = nullptr;
+    uint64_t n_fasta = 0;
+    DevBuf fasta_own;
+    // FASTQ input (fk_set_input_format): the device input is normalised in place to text the FASTA
+    // parsers read (fk_fastq.inc), record-aligned range after range, each byte once
+    int32_t in_format = FK_FORMAT_FASTA, fq_min_q = 0, fq_q_off = 33;  // the next job's
+    bool job_open = false;      // between a job's first ingest and its fk_map / fk_finish
+    bool fq_job = false;        // the current input is FASTQ
+    uint64_t fq_done = 0;       // the frontier: bytes [0, fq_done) are normalised (and may be mapped)
+    std::vector<uint8_t> fq_tail;  // host copy of the caller's bytes [fq_done, n_fasta) (a record straddling two calls)
+    bool fq_launched = false;   // a normalise launch of this job has been queued
+    DevBuf fq_ws, fq_info;      // launch workspace; the job's records, masked bases, ~(first bad record), overflow
+    PinBuf fq_pin;              // fq_info read back with the map's counters
+    bool fq_have_info = false;  // fk_fastq_info has figures (a FASTQ job was mapped)
+    uint64_t fq_out[3] = {0, 0, UINT64_MAX};
+    std::vector<hipEvent_t> fq_evs;  // begin / end of every normalise launch of the job (fk_debug_fastq_ms)
+    size_t fq_nev = 0;
+
+    // parse + encode
+    DevBuf tile_last_nl, tile_off, npos_dev, codes, valid;
+    // signature
+    DevBuf records, counters, sig_status, sig_kmers;
+    DevBuf tcnt;                  // fused map: records per tile (tiled record layout)
+    DevBuf rec_hdr;               // fused map: every record's header word, in the record's tile slot
+    DevBuf rec_pos;               // fused map: every record's first position in its tile's code stream (u16)
+    DevBuf rec_code;              // fused map: per tile, the tile's 2-bit code stream (map_fused_cslot() words)
+    DevBuf tstat;                 // fused map: per tile (k-mers, positions)
+    DevBuf map_vslots;            // split map: the parse kernel's valid streams for the passes (MAP_VSLOT_TILES tiles)
+    bool rec_tiled = false;       // records: the fused map's tiles (else dense, c->nrec)
+    uint64_t rec_tiles = 0;       // tiles of the tiled layout
+    uint64_t nrec = 0, nkmers = 0;
+    bool mapped = false;
+    // destination partition (n_ranks > 1)
+    std::vector<uint64_t> send_counts;
+    // reduce
+    PartBufs dest, part, binhist;  // record partition by destination rank (fk_map) / by local bin (fk_reduce)
+    DevBuf precs, chunks, bin_chunk_begin;
+    std::vector<uint32_t> h_bcb;  // bin_chunk_begin on the host (the last uploaded chunk table)
+    DevBuf hpieces, hpiece_first, hpiece_tot;  // k_expand_hist_piece: bins split into pieces of chunks
+    DevBuf chunk_nk, chunk_base, lp, cell_total, cell_base, flags, flag_scan, buckets, keys, out_keys, out_counts;
+    DevBuf scratch;
+    DevBuf bucket_unique, dense_off, dense_keys, dense_counts, bin_off, misc, tier_list, mid, sc_total;
+    DevBuf sp_base, sp_keys, sp_subs, sp_par, sp_fb;  // heavy buckets split into sub-buckets
+    DevBuf mid_fb;  // mid-tier buckets left to the 1024-key kernel by the ranges kernel
+    ScanWorkspace ws;
+    // results
+    bool have_result = false;
+    uint64_t distinct = 0;
+    std::vector<uint64_t> h_bin_off;  // [nlb + 1]
+    fk_stats stats{};
+    // events: 0/1 parse, 2/3 signature, 4/5 partition, 6/7 count, 8/9 encode kernel, 10/11 sig kernel
+    hipEvent_t ev[12] = {};
+    double ms_h2d = 0.0;  // last fk_ingest: first copy issued -> last copy done
+    bool ev_parse = false, ev_sig = false, ev_part = false, ev_count = false;
+    std::vector<hipEvent_t> seg_evs;  // fk_ingest, pinned source: one "segment landed" event per segment
+    std::vector<hipEvent_t> map_evs;  // ... and one "segment mapped" event (one rank's staged pieces)
+    std::vector<uint64_t> seg_tiles;  // ... the tiles mapped once that segment's map is done
+    PinBuf pin_up, pin_down;              // staging: chunk tables up, per-bin counts down
+    hipEvent_t pin_up_ev = nullptr;       // the last upload out of pin_up (on whichever stream queued it)
+    bool pin_up_busy = false;             // ... was queued and not yet waited for
+    PinBuf pin_tier;                      // the bucket tiers' sizes, read while the wave tier runs
+    PinBuf file_pin[2];                   // fk_ingest_file_range: the split read in pinned windows
+    hipEvent_t tier_ev = nullptr;         // ... once this copy has landed
+    bool distinct_pending = false;        // the sorted count's distinct total arrives with the bin offsets
+    // The sorted count's result is bucket-major ("gapped"): bucket q's distinct keys ascending at its
+    // first slot buckets[q].begin of res_keys / out_counts, dense_off[q] = their exclusive offset in the
+    // bin-ordered result, bin_off / h_bin_off per bin.  Readers gather a bin's buckets (fk_get_bin) or
+    // the whole result (fk_write_bins).
+    bool gapped = false, dense_ready = false;
+    const uint64_t *res_keys = nullptr;   // okb of the last sorted count (out_keys, or mid)
+    const uint64_t *res_fs = nullptr;     // flag_scan of its bucket cut
+    uint64_t res_nbuckets = 0;
+    int res_F = 0;
+    ViewBufs vw;
+    // "this context's result is complete", recorded on its stream when another context's comparison looks k-mers up in it
+    hipEvent_t cmp_ev = nullptr;
+
+    // multi-rank exchange inside the context (fk_comm_init / fk_comm_init_local): the input
+    // is emitted in pieces grouped by (destination, local bin) and each piece is exchanged
+    // while the next one is still being copied in; fk_finish sends the last piece, then
+    // counts every received segment (the reduceByKey shuffle of SBKC:1034-1042)
+    // staged pieces (one rank, or the received segments with a communicator; sorted count, k <= 63):
+    // each piece of the input is partitioned and expanded into its own key array while later pieces
+    // land; the job's buckets are counted once over every piece's keys (no per-piece count, no merge)
+    bool pieces_void = false;     // a fallback or a retract: the job is counted whole at the end
+    uint64_t tiles_counted = 0;   // one rank: tiled records [0, tiles_counted) staged
+    uint64_t job_bytes = 0;       // one rank: the job's input size when one fk_ingest call holds it all, or
+                                  // announced by fk_ingest_reserve (0: unknown)
+    uint64_t reserve_bytes = 0;   // fk_ingest_reserve's size for the next job
+    size_t segs_counted = 0;      // with a communicator: received segments [0, segs_counted) staged
+    std::vector<double> st_cuts{0.4, 0.7, 0.9};  // piece ends of a staged job (FASTKMER_PIECE_CUTS; 45 / 70 / 85 % measured 22.84 vs 22.77 ms)
+    // ... of a 64-bit job of >= 4 GB without FASTKMER_PIECE_CUTS: five pieces, the last 7 % (configs[2]
+    // load 146.2 -> 145.4 ms, profiles/r06z_five_pieces.txt; configs[1]'s 1 GB keeps four)
+    std::vector<double> st_cuts5{0.38, 0.64, 0.82, 0.93};
+    bool cuts_env = false;
+    // ... with a communicator: earlier, a received piece lands a step's partition and transfer later
+    // (one in-process rank at the configs[2] load: 153.2-153.7 ms against 156.1-159.4 with the local
+    // cuts, profiles/r05z_xch_cuts_seg_ab.txt)
+    std::vector<double> xst_cuts{0.35, 0.65, 0.84};
+    uint32_t st_np = 0;                          // pieces expanded in the current job
+    uint32_t st_cut = 0;                         // one rank: st_cuts passed in the current job
+    SortedPlan st_plan;                          // the job's cells (fixed by its first piece)
+    uint64_t st_kmers = 0;                       // k-mers expanded so far
+    DevBuf st_keys[STAGE_MAXP], st_cb[STAGE_MAXP], st_total, piece_starts;
+    hipEvent_t st_ev[4 * STAGE_MAXP] = {};       // per piece: partition begin / end, expansion begin / end
+
+    fk::Comm *comm = nullptr;
+    hipStream_t comm_stream = nullptr;
+    uint32_t *hold_flag = nullptr;               // fk_debug_comm_hold: host-mapped release flag
+    // staging of received segments on its own stream (each waits for its step's transfer, so the map
+    // stream never does) with its own scan workspace; the count waits for it
+    hipStream_t xstage = nullptr;
+    hipEvent_t xstage_ev = nullptr;
+    ScanWorkspace ws_x;
+    StreamWs main_on() { return StreamWs{stream, &ws}; }
+    StreamWs stage_on() { return StreamWs{xstage, &ws_x}; }
+    hipEvent_t emit_ev = nullptr;                // map stream: a piece's send records are written
+    std::vector<hipEvent_t> xev;                 // comm stream: begin / end of every piece's transfer
+    uint64_t piece_bytes = 512ull << 20;         // FASTKMER_PIECE_BYTES: FASTA bytes per piece (with a
+                                                 // communicator: a tenth of a known job, 128 MB .. 1 GB)
+    bool piece_bytes_set = false;
+    uint64_t ingest_seg = 32ull << 20;           // FASTKMER_INGEST_SEG: H2D segment of a pinned source
+    DevBuf xsend, xrecv;                         // send ring (pieces in flight), received records
+    struct XSeg {                                // received records of one (piece, sender)
+        uint64_t off;                            // first record in xrecv
+        int32_t sender;
+        uint64_t step;                           // the exchange step that delivered it
+        std::vector<uint64_t> rec, kmer;         // per local bin
+    };
+    struct Xch {
+        bool open = false;           // a job's exchange has started (pieces sent)
+        bool sent_final = false;     // this rank has sent its last piece
+        bool all_final = false;      // every rank has sent its last piece
+        bool stop_pieces = false;    // the fused map fell back: the rest goes in fk_finish, earlier pieces retracted
+        uint64_t tiles_sent = 0;     // tiled records [0, tiles_sent) emitted in pieces
+        uint64_t send_used = 0, recv_used = 0;  // records
+        uint64_t pieces = 0, bytes_sent = 0, bytes_received = 0, expect_bytes = 0;
+        std::vector<XSeg> segs;
+    } xch;
+};
+
+// How bins map to ranks and to a rank's local bins (default placement, or fk_set_bin_owners).
+inline const uint32_t *owner_table(const fk_ctx *c) { return c->custom_owners ? c->d_owner.as<uint32_t>() : nullptr; }
+inline const uint32_t *local_table(const fk_ctx *c) { return c->custom_owners ? c->d_local.as<uint32_t>() : nullptr; }
+inline int32_t global_bin(const fk_ctx *c, uint32_t lb) {
+    return c->custom_owners ? c->h_lbin_bin[lb] : (int32_t)(c->cfg.rank + lb * c->G);
+}
+inline bool owns(const fk_ctx *c, int32_t b) {
+    if (b < 0 || b >= c->Bc) return false;
+    return c->custom_owners ? c->h_owner[b] == c->cfg.rank : (uint32_t)b % c->G == (uint32_t)c->cfg.rank;
+}
+inline uint32_t local_bin(const fk_ctx *c, int32_t b) { return c->custom_owners ? c->h_bin_lbin[b] : (uint32_t)b / c->G; }
+inline int32_t bin_owner(const fk_ctx *c, int32_t b) {
+    return c->custom_owners ? c->h_owner[b] : (int32_t)((uint32_t)b % c->G);
+}

@@ -1,12 +1,12 @@
 // fk_query.inc: k-mer count lookups in the sorted count's result -- included by fk_kernels.hip
 // inside namespace fk.
 // ---------------------------------------------------------------------------
-// 7. lookups (fk_query*, no reference counterpart).  The result stays bucket-major (fk_api.cpp,
-//    sorted_result): bucket q holds the cells [c0, c1) of one local bin, its distinct keys lie
-//    ascending at res_keys + KW * begin with their counts at out_counts + begin, dense_off[q + 1] -
-//    dense_off[q] of them (a heavy bucket's sub-buckets are written in splitter order one after
-//    the other, k_sub_count64_seq / k_sub_count128_seq, so the whole bucket ascends).  One lane per
-//    query:
+// 7. lookups (fk_query*, no reference counterpart; their host side is fk_views.cpp).  The result
+//    stays bucket-major (the count's sorted_result, fk_api.cpp): bucket q holds the cells [c0, c1) of
+//    one local bin, its distinct keys lie ascending at res_keys + KW * begin with their counts at
+//    out_counts + begin, dense_off[q + 1] - dense_off[q] of them (a heavy bucket's sub-buckets are
+//    written in splitter order one after the other, k_sub_count64_seq / k_sub_count128_seq, so the
+//    whole bucket ascends).  One lane per query:
 //      key -> reverse complement -> canonical key, signature (kmer_signature) -> bin -> owner and
 //      local bin -> cell = top F bits -> g = (lbin << F) + cell -> bucket -> binary search.
 //    The bucket of cell g: flag_scan is the exclusive scan of the bucket-start flags with the

@@ -1,8 +1,9 @@
 // fk_spectrum.inc: abundance spectrum and count-range views of the counted result -- included by
 // fk_kernels.hip inside namespace fk.
 // ---------------------------------------------------------------------------
-// 8. spectrum and count ranges (fk_spectrum*, fk_*_range, no reference counterpart).  Both count
-//    modes leave the result bucket-major (fk_api.cpp, sorted_result): bucket q's distinct keys at
+// 8. spectrum and count ranges (fk_spectrum*, fk_*_range, no reference counterpart; their host side
+//    is fk_views.cpp).  Both count modes leave the result bucket-major (the count's sorted_result,
+//    fk_api.cpp): bucket q's distinct keys at
 //    res_keys + KW * buckets[q].begin, their counts at out_counts + buckets[q].begin,
 //    dense_off[q + 1] - dense_off[q] of them; use_ht only changes the order inside a bucket.  The
 //    arrays have gaps (a bucket's slots are its keys, not its distinct keys), so every kernel

@@ -2,7 +2,7 @@
 runs on fk_config.device, whatever device the calling thread has current).
 
 Every exported call that touches the GPU selects the context's device and
-restores the caller's (fk_api.cpp DeviceGuard).  These tests use a context
+restores the caller's (fk_ctx.h DeviceGuard).  These tests use a context
 from a thread other than the one that created it (the JNI shim's executor
 threads do that) and, on a box with two GPUs, two contexts on different
 devices driven alternately from one thread.
