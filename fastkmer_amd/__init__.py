@@ -202,6 +202,9 @@ def lib():
         "fk_debug_fingerprint_bits": (ctypes.c_int, [I32, I32]),
         "fk_debug_wave_count": (ctypes.c_int, [I32, I32, I32, ctypes.c_uint32, ctypes.c_uint32, I32, P,
                                                ctypes.c_uint32, P, P, P]),
+        "fk_debug_wave_count_w": (ctypes.c_int, [I32, I32, I32, ctypes.c_uint32, ctypes.c_uint32, I32, P,
+                                                 ctypes.c_uint32, P, P, P]),
+        "fk_debug_fold_stats": (ctypes.c_int, [P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -885,18 +888,29 @@ class KmerCounter:
         _check(lib().fk_get_stats(self._h, ctypes.byref(st)))
         return {n: getattr(st, n) for n, _ in fk_stats._fields_}
 
+    def fold_stats(self) -> dict:
+        """Test hook (fk_debug_fold_stats): the fold of the last finish()'s landed pieces -- pieces
+        folded, their k-mers, the weighted entries they became, and the first piece's sampled
+        entries per k-mer (None: no sample was taken)."""
+        out = (ctypes.c_uint64 * 4)()
+        _check(lib().fk_debug_fold_stats(self._h, out))
+        return {"pieces_folded": int(out[0]), "entries_in": int(out[1]), "entries_out": int(out[2]),
+                "sample_ratio": int(out[3]) / 1e6 if out[3] else None}
 
-def debug_wave_count(keys: np.ndarray, k: int, F: int, c0: int, c1: int, slots: int, device: int = 0):
+
+def debug_wave_count(keys: np.ndarray, k: int, F: int, c0: int, c1: int, slots: int, device: int = 0,
+                     weighted: bool = False):
     """Test hook (fk_debug_wave_count): one bucket of keys (uint64; (hi, lo) rows
-    for k > 32) through the wave-tier count kernel; returns (distinct keys, counts)."""
+    for k > 32) through the wave-tier count kernel; returns (distinct keys, counts).
+    weighted (fk_debug_wave_count_w): k <= 30 keys may hold weight - 1 in bits [2k, 2k + 4)."""
     kw = 1 if k <= 32 else 2
     keys = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1, kw)
     n = len(keys)
     ok = np.zeros(n * kw, dtype=np.uint64)
     oc = np.zeros(n, dtype=np.uint32)
     nout = ctypes.c_uint32(0)
-    _check(lib().fk_debug_wave_count(device, k, F, c0, c1, slots, keys.ctypes.data, n, ok.ctypes.data,
-                                     oc.ctypes.data, ctypes.byref(nout)))
+    fn = lib().fk_debug_wave_count_w if weighted else lib().fk_debug_wave_count
+    _check(fn(device, k, F, c0, c1, slots, keys.ctypes.data, n, ok.ctypes.data, oc.ctypes.data, ctypes.byref(nout)))
     u = nout.value
     return (ok[:u] if kw == 1 else ok[:2 * u].reshape(-1, 2)), oc[:u]
 

@@ -252,8 +252,9 @@ FK_EXPORT int fk_create(const fk_config *cfg, fk_ctx **out) {
     c->W = cfg->k <= 32 ? 2 : 3;
     c->KW = cfg->k <= 32 ? 1 : 2;
     c->fm = make_fastmod((uint32_t)c->Bc);
-    // The product library reads eleven variables: three sizes of the streamed input, the lookups' staging
-    // chunk (FASTKMER_QUERY_CHUNK, read by every fk_query / fk_query_sequence call) and seven test
+    // The product library reads thirteen variables: three sizes of the streamed input, the fold's gate
+    // (FASTKMER_FOLD), the lookups' staging chunk (FASTKMER_QUERY_CHUNK, read by every fk_query /
+    // fk_query_sequence call) and eight test
     // hooks that steer small inputs onto paths only large or adversarial inputs reach (all
     // result-preserving).  Timing probes that alter results exist only in a library built with
     // -DFK_PROBES (python -m fastkmer_amd.build --probes).
@@ -283,6 +284,9 @@ FK_EXPORT int fk_create(const fk_config *cfg, fk_ctx **out) {
     if (const char *v = env("FASTKMER_DEBUG_MID_PARTS")) c->mid_parts = atoi(v);  // test hook: 1 / 2 / 0
     if (const char *v = env("FASTKMER_DEBUG_SPLIT_RETRY")) c->split_retry = v[0] == '1';  // test hook
     if (const char *v = env("FASTKMER_DEBUG_SPECTRUM_WIDE")) c->spectrum_wide = v[0] == '1';  // test hook
+    if (const char *v = env("FASTKMER_FOLD")) c->fold_mode = std::clamp(atoi(v), 0, 2);
+    if (const char *v = env("FASTKMER_DEBUG_FOLD_WMAX"))  // test hook
+        c->fold_wmax = (uint32_t)std::clamp(atoi(v), 1, (int)WKEY_WMAX);
     if (const char *v = env("FASTKMER_X2_L1")) c->x2_l1 = atoi(v);
     if (const char *v = env("FASTKMER_FUSED")) c->fused = atoi(v);
 #ifdef FK_PROBES
@@ -397,6 +401,7 @@ FK_EXPORT void fk_destroy(fk_ctx *c) {
     c->pin_up.release();
     c->pin_down.release();
     c->pin_tier.release();
+    c->fold_pin.release();
     c->file_pin[0].release();
     c->file_pin[1].release();
     if (c->tier_ev) (void)hipEventDestroy(c->tier_ev);
@@ -428,6 +433,7 @@ FK_EXPORT void fk_destroy(fk_ctx *c) {
         if (ev) (void)hipEventDestroy(ev);
     for (int p = 0; p < STAGE_MAXP; ++p) release(c->st_keys[p]), release(c->st_cb[p]);
     release(c->st_total);
+    release(c->fold_cnt), release(c->fold_cb), release(c->fold_io);
     release(c->piece_starts);
     if (c->seg_ev) (void)hipEventDestroy(c->seg_ev);
     for (auto &ev : c->h2d_ev)
@@ -1646,7 +1652,7 @@ static hipError_t launch_split(const BucketCount &t, const uint32_t *l1, uint32_
 static hipError_t launch_sub_count_seq(const BucketCount &t, const uint32_t *l1, uint32_t nl, const SubBucket *subs,
                                        hipStream_t s) {
     return launch_sub_count64_seq(t.buckets(), l1, nl, t.c->sp_par.as<SplitParent>(), subs, t.c->sp_keys.as<uint64_t>(),
-                                  t.out_keys(), t.out_counts(), t.unique(), s, t.ordered);
+                                  t.k, t.src.weighted, t.out_keys(), t.out_counts(), t.unique(), s, t.ordered);
 }
 static hipError_t launch_sub_count_seq(const BucketCount &t, const uint32_t *l1, uint32_t nl, const SubBucket128 *subs,
                                        hipStream_t s) {
@@ -1701,7 +1707,7 @@ static int bucket_cut(BucketCount &t, const SortedPlan &pl, uint64_t total_kmers
     src.F = F;
     if (src.np > 0) FK_TRY(ensure(*B.piece_starts, nbuckets * sizeof(PieceStarts)));
     // the buckets' sizes, and the staged pieces' starts per bucket (read by the wave tier)
-    HIP_TRY(launch_bucket_finish(src, B.buckets->as<Bucket>(), nbuckets, c->nlb, total_kmers,
+    HIP_TRY(launch_bucket_finish(src, B.buckets->as<Bucket>(), nbuckets, c->nlb, cell_base + ncell_all,
                                  src.np > 0 ? B.piece_starts->as<PieceStarts>() : nullptr, cs));
     if (src.np > 0) src.starts = B.piece_starts->as<PieceStarts>();
     HIP_TRY(hipMemsetAsync(c->misc.p, 0, 64, cs));
@@ -2271,6 +2277,10 @@ static void pieces_reset(fk_ctx *c) {
     c->pieces_void = false;
     c->tiles_counted = 0;
     c->segs_counted = 0;
+    c->fold_decided = c->fold_on = false;
+    c->fold_sample_ppm = 0;
+    c->fold_in = 0;
+    c->fold_pieces.clear();
 }
 
 // Staged pieces per job: 128-bit keys at most STAGE_MAXP128 (their kernels' piece loops stop there)
@@ -2357,6 +2367,7 @@ static int staged_count(fk_ctx *c, hipStream_t cut) {
                               c->cell_base.as<uint64_t>() + ncell_all, *on.ws, cs));
     BucketSrc src{nullptr, pl.F};
     src.np = (int)c->st_np;
+    src.weighted = !c->fold_pieces.empty();
     for (uint32_t p = 0; p < c->st_np; ++p) {
         src.pk[p] = c->st_keys[p].as<uint64_t>();
         src.pcb[p] = c->st_cb[p].as<uint64_t>();
@@ -2398,6 +2409,93 @@ static bool local_piece_due(const fk_ctx *c, uint64_t tiles) {
     return c->st_np < 3 && (tiles - c->tiles_counted) * tile >= c->piece_bytes;
 }
 
+// ---- the fold of a landed piece (fk_fold.inc)
+// A job folds at all: one rank's staged pieces of 64-bit keys with a weight field (2k <= 60)
+static bool fold_eligible(const fk_ctx *c) {
+    return c->fold_mode != 0 && c->KW == 1 && 2 * c->cfg.k <= WKEY_MAX_BITS && staged_eligible(c);
+}
+
+// The gate of FASTKMER_FOLD=1, once per job behind its first piece's expansion: a count-only pass of
+// the fold over one super-cell in FOLD_SAMPLE_STRIDE (an odd stride: a bin holds a power of two of
+// them, and every 64th would be the same few of every bin; at most ~FOLD_SAMPLE_MAX super-cells, so
+// that a large piece's sample stays a few tens of microseconds on a staging stream with no idle time:
+// one in 61 of the configs[2] load's first piece took 0.25 ms) gives the entries per key the piece folds
+// to; the job's pieces are folded when that ratio is at most FOLD_MAX_PPM.  The host waits for the
+// figure (the piece's expansion): the copies and the maps of the whole call are queued already.
+constexpr uint32_t FOLD_SAMPLE_STRIDE = 61;
+constexpr uint64_t FOLD_SAMPLE_MAX = 4096;
+constexpr uint64_t FOLD_MAX_PPM = 600000;
+static int fold_decide(fk_ctx *c, StreamWs on, uint32_t p) {
+    c->fold_decided = true;
+    c->fold_on = c->fold_mode == 2;
+    if (c->fold_mode != 1) return FK_OK;
+    const SortedPlan &pl = c->st_plan;
+    FK_TRY(ensure(c->fold_io, 16));
+    const uint64_t nsc = (uint64_t)c->nlb << pl.F1;
+    const uint32_t stride = (uint32_t)std::max<uint64_t>(FOLD_SAMPLE_STRIDE, (nsc / FOLD_SAMPLE_MAX) | 1ull);
+    HIP_TRY(hipMemsetAsync(c->fold_io.p, 0, 16, on.s));
+    HIP_TRY(launch_fold_sample(c->st_keys[p].as<uint64_t>(), c->st_cb[p].as<uint64_t>(), c->nlb, c->cfg.k, pl.F, pl.F2,
+                               c->fold_wmax, stride, c->fold_io.as<unsigned long long>(), on.s));
+    uint64_t io[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(io, c->fold_io.p, 16, hipMemcpyDeviceToHost, on.s));
+    HIP_TRY(hipStreamSynchronize(on.s));
+    c->fold_sample_ppm = io[0] ? io[1] * 1000000ull / io[0] : 1000000ull;
+    c->fold_on = io[0] && c->fold_sample_ppm <= FOLD_MAX_PPM;
+    htrace("staged: fold sampled");
+    return FK_OK;
+}
+
+// The finished job's fold figures (fk_debug_fold_stats): pieces folded, their keys, their entries,
+// the sample's entries per million keys.  counted = false: the pieces were dropped (counted whole).
+static void fold_report(fk_ctx *c, bool counted) {
+    uint64_t out = 0;
+    for (uint32_t p : c->fold_pieces) out += c->fold_pin.as<uint64_t>()[p];
+    c->fold_last[0] = counted ? c->fold_pieces.size() : 0;
+    c->fold_last[1] = counted ? c->fold_in : 0;
+    c->fold_last[2] = counted ? out : 0;
+    c->fold_last[3] = c->fold_sample_ppm;
+}
+
+// Which pieces of a folding job (staged by local_maybe_piece, st_cut counting this one): with
+// FASTKMER_FOLD=2 every one; else, of a job cut by its size, the first piece only.  A fold holds
+// the staging stream, and only the first piece leaves it idle long enough (configs[1]: 3 ms between
+// the end of its expansion and the next piece's last byte; the second piece's expansion ends 0.4 ms
+// before the third lands): a later fold delays every piece behind it and, through them, the tail it
+// was meant to shorten (profiles/r07_fold_c2_timeline_all_pieces.txt: the last piece 4.4 ms late).
+static bool fold_piece_due(const fk_ctx *c) {
+    if (c->fold_mode == 2) return true;
+    if (c->job_bytes && !c->piece_bytes_set) return c->st_cut == 1;
+    return true;
+}
+
+// Folds staged piece p (just expanded on `on`, pk keys): k_fold_sc into `mid` (dead since the piece's
+// level 2), the scan of the entries per cell into the piece's new cell offsets, k_fold_compact back
+// into st_keys[p]; st_total, which took the piece's raw cell totals, is corrected to the entries.
+// The piece's raw k-mer count stays an upper bound of its entries wherever a size is needed.
+static int fold_piece(fk_ctx *c, StreamWs on, uint32_t p, uint64_t pk) {
+    if (pk == 0 || pk >= (1ull << 32)) return FK_OK;  // u32 entries per cell
+    const SortedPlan &pl = c->st_plan;
+    const uint64_t ncell_all = (uint64_t)c->nlb << pl.F;
+    FK_TRY(ensure(c->fold_cnt, ncell_all * 4));
+    FK_TRY(ensure(c->fold_cb, (ncell_all + 1) * 8));
+    HIP_TRY(launch_fold_sc(c->st_keys[p].as<uint64_t>(), c->st_cb[p].as<uint64_t>(), c->nlb, c->cfg.k, pl.F, pl.F2,
+                           c->fold_wmax, c->mid.as<uint64_t>(), c->fold_cnt.as<uint32_t>(), on.s));
+    HIP_TRY(scan_excl_sum_u32_to_u64(c->fold_cnt.as<uint32_t>(), c->fold_cb.as<uint64_t>(), ncell_all,
+                                     c->fold_cb.as<uint64_t>() + ncell_all, *on.ws, on.s));
+    HIP_TRY(launch_fold_compact(c->mid.as<uint64_t>(), c->st_cb[p].as<uint64_t>(), c->fold_cb.as<uint64_t>(),
+                                c->fold_cnt.as<uint32_t>(), c->nlb, pl.F, pl.F2, c->st_keys[p].as<uint64_t>(),
+                                c->st_total.as<uint64_t>(), on.s));
+    // the piece's entries, for fk_debug_fold_stats (read once the job is counted; nobody waits for it)
+    if (c->fold_pin.ensure(8 * STAGE_MAXP)) return set_err(FK_E_NOMEM, "hipHostMalloc failed");
+    HIP_TRY(hipMemcpyAsync(c->fold_pin.as<uint64_t>() + p, c->fold_cb.as<uint64_t>() + ncell_all, 8,
+                           hipMemcpyDeviceToHost, on.s));
+    std::swap(c->st_cb[p], c->fold_cb);  // stream order: the raw offsets are overwritten by the next fold's scan
+    c->fold_in += pk;
+    c->fold_pieces.push_back(p);
+    htrace("staged: piece folded");
+    return FK_OK;
+}
+
 // tiles: the tiles mapped once `mapped` (recorded on the map stream) has passed.  The piece is
 // partitioned and expanded on the staging stream, which fk_finish joins (xstage_ev).
 static int local_maybe_piece(fk_ctx *c, uint64_t tiles, hipEvent_t mapped) {
@@ -2416,8 +2514,15 @@ static int local_maybe_piece(fk_ctx *c, uint64_t tiles, hipEvent_t mapped) {
     const RecSrc src = fused_src(c, t0, nt, nt * map_fused_tcap());
     c->tiles_counted = tiles;
     c->st_cut += 1;
+    const uint32_t p = c->st_np;
+    const uint64_t k0 = c->st_kmers;
     FK_TRY(staged_expand(c, on, nullptr, src,
                          c->job_bytes ? (double)(nt * fm_tile_bytes(FUSED_NT)) / (double)c->job_bytes : 0.0));
+    // a piece staged here is never the job's last (fk_finish stages that one): fold it while the rest lands
+    if (c->st_np > p && fold_eligible(c)) {
+        if (!c->fold_decided) FK_TRY(fold_decide(c, on, p));
+        if (c->fold_on && fold_piece_due(c)) FK_TRY(fold_piece(c, on, p, c->st_kmers - k0));
+    }
     HIP_TRY(hipEventRecord(c->xstage_ev, s));
     return FK_OK;
 }
@@ -2827,9 +2932,11 @@ static int finish_local(fk_ctx *c) {
         if (rc == FK_OK) rc = staged_count(c, cut);
         if (cut) (void)hipStreamSynchronize(cut);
         FK_TRY(rc);
+        fold_report(c, true);
         pieces_reset(c);
         return FK_OK;
     }
+    fold_report(c, false);
     pieces_reset(c);
     return reduce_src(c, map_src(c));
 }
@@ -3076,9 +3183,10 @@ FK_EXPORT int fk_debug_comm_release(fk_ctx *c) {
 // ---------------------------------------------------------------------------
 // test hook: one bucket through the wave tier (k_bucket_count64_wave / k_bucket_count128_wave)
 // ---------------------------------------------------------------------------
-FK_EXPORT int fk_debug_wave_count(int32_t device, int32_t k, int32_t F, uint32_t c0, uint32_t c1, int32_t slots,
-                                  const uint64_t *keys, uint32_t n, uint64_t *out_keys, uint32_t *out_counts,
-                                  uint32_t *n_out) {
+// weighted: a 64-bit key may carry a weight field (bits [2k, 2k + 4), 2k <= WKEY_MAX_BITS)
+static int debug_wave_count(int32_t device, int32_t k, int32_t F, uint32_t c0, uint32_t c1, int32_t slots,
+                            const uint64_t *keys, uint32_t n, uint64_t *out_keys, uint32_t *out_counts,
+                            uint32_t *n_out, bool weighted) {
     if (!keys || !out_keys || !out_counts || !n_out || k < 1 || k > 63 || F < 1 || F > MAX_FINE_BITS || c1 <= c0 ||
         c1 > (1u << F))
         return set_err(FK_E_INVALID, "bad argument");
@@ -3089,7 +3197,10 @@ FK_EXPORT int fk_debug_wave_count(int32_t device, int32_t k, int32_t F, uint32_t
         return set_err(FK_E_INVALID, "slots: %u (k <= 32) or 384 (k > 32)", WAVE_SLOTS);
     const int sh = 2 * k - F;
     for (uint32_t i = 0; i < n; ++i) {  // every key inside the bucket's cells
-        const uint64_t hi = KW == 1 ? 0 : keys[2 * i], lo = KW == 1 ? keys[i] : keys[2 * i + 1];
+        const uint64_t hi = KW == 1 ? 0 : keys[2 * i];
+        uint64_t lo = KW == 1 ? keys[i] : keys[2 * i + 1];
+        if (weighted && KW == 1 && 2 * k <= WKEY_MAX_BITS && (lo >> (2 * k)) <= WKEY_WMAX - 1)
+            lo &= (1ull << (2 * k)) - 1ull;  // the weight field; whatever else lies above the k-mer is refused below
         const uint64_t cell = sh >= 64 ? (hi >> (sh - 64)) : (sh == 0 ? lo : ((hi << (64 - sh)) | (lo >> sh)));
         if ((KW == 1 && k < 32 && (lo >> (2 * k)) != 0) || cell < c0 || cell >= c1)
             return set_err(FK_E_RANGE, "key %u lies outside cells [%u, %u)", i, c0, c1);
@@ -3102,11 +3213,13 @@ FK_EXPORT int fk_debug_wave_count(int32_t device, int32_t k, int32_t F, uint32_t
     FK_TRY(ensure(du, 16));
     FK_TRY(ensure(db, sizeof(Bucket)));
     const Bucket b{0, n, 0, c0, c1};
+    BucketSrc wsrc{dk.as<uint64_t>(), F};
+    wsrc.weighted = weighted;
     int rc = FK_OK;
     hipError_t e = hipMemcpy(dk.p, keys, (uint64_t)n * 8 * KW, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(db.p, &b, sizeof(Bucket), hipMemcpyHostToDevice);
     if (e == hipSuccess)
-        e = KW == 1 ? launch_bucket_count64_wave(BucketSrc{dk.as<uint64_t>(), F}, db.as<Bucket>(), 1, k, dok.as<uint64_t>(),
+        e = KW == 1 ? launch_bucket_count64_wave(wsrc, db.as<Bucket>(), 1, k, dok.as<uint64_t>(),
                                                  doc.as<uint32_t>(), du.as<uint64_t>(), nullptr, nullptr)
                     : launch_bucket_count128_wave(BucketSrc{dk.as<uint64_t>(), F}, db.as<Bucket>(), 1, k, dok.as<uint64_t>(),
                                                   doc.as<uint32_t>(), du.as<uint64_t>(), nullptr);
@@ -3118,6 +3231,24 @@ FK_EXPORT int fk_debug_wave_count(int32_t device, int32_t k, int32_t F, uint32_t
     else if (U > n) rc = set_err(FK_E_INVALID, "bucket reported %llu distinct keys of %u", (unsigned long long)U, n);
     *n_out = (uint32_t)U;
     return rc;
+}
+
+FK_EXPORT int fk_debug_wave_count(int32_t device, int32_t k, int32_t F, uint32_t c0, uint32_t c1, int32_t slots,
+                                  const uint64_t *keys, uint32_t n, uint64_t *out_keys, uint32_t *out_counts,
+                                  uint32_t *n_out) {
+    return debug_wave_count(device, k, F, c0, c1, slots, keys, n, out_keys, out_counts, n_out, false);
+}
+
+FK_EXPORT int fk_debug_wave_count_w(int32_t device, int32_t k, int32_t F, uint32_t c0, uint32_t c1, int32_t slots,
+                                    const uint64_t *keys, uint32_t n, uint64_t *out_keys, uint32_t *out_counts,
+                                    uint32_t *n_out) {
+    return debug_wave_count(device, k, F, c0, c1, slots, keys, n, out_keys, out_counts, n_out, true);
+}
+
+FK_EXPORT int fk_debug_fold_stats(const fk_ctx *c, uint64_t out[4]) {
+    if (!c || !out) return set_err(FK_E_INVALID, "null argument");
+    std::copy(c->fold_last, c->fold_last + 4, out);
+    return FK_OK;
 }
 
 // measurement hook (a library built with -DFK_PROBES; FK_E_STATE otherwise): the fused map's

@@ -469,18 +469,20 @@ __device__ __forceinline__ BucketView bucket_view_starts(const BucketSrc &src, c
 }
 
 // Each bucket's size and end cell from the next bucket's start (k_bucket_write leaves n = c1 = 0)
-// and, with staged pieces, its piece starts.  One bucket per thread; bucket i ends where i + 1
+// and, with staged pieces, its piece starts.  The last bucket ends at *total_keys, the last word of
+// the cell offsets' scan (folded pieces hold fewer keys than the job has k-mers: the host's count
+// would not do).  One bucket per thread; bucket i ends where i + 1
 // starts (every bin's first bucket starts at its cell 0), so a piece's cell offset at the end comes
 // from the next lane's read (the wave's last lane reads its own).
 template <bool PIECES>
 __global__ __launch_bounds__(NT) void k_bucket_finish(BucketSrc src, Bucket *__restrict__ buckets, uint64_t nb,
-                                                      uint32_t nlbins, uint64_t total_keys,
+                                                      uint32_t nlbins, const uint64_t *__restrict__ total_keys,
                                                       PieceStarts *__restrict__ out) {
     const uint64_t i = (uint64_t)blockIdx.x * NT + threadIdx.x;
     const bool mine = i < nb;  // every lane takes part in the shuffles below
     const uint32_t ncell = 1u << src.F;
     Bucket b{};
-    uint64_t e_beg = total_keys, g1 = (uint64_t)nlbins << src.F;
+    uint64_t e_beg = *total_keys, g1 = (uint64_t)nlbins << src.F;
     if (mine) {
         b = buckets[i];
         if (i + 1 < nb) {
@@ -515,7 +517,7 @@ __global__ __launch_bounds__(NT) void k_bucket_finish(BucketSrc src, Bucket *__r
 }
 
 hipError_t launch_bucket_finish(const BucketSrc &src, Bucket *buckets, uint64_t nb, uint32_t nlbins,
-                                uint64_t total_keys, PieceStarts *out, hipStream_t s) {
+                                const uint64_t *total_keys, PieceStarts *out, hipStream_t s) {
     if (!nb) return hipSuccess;
     const unsigned grid = (unsigned)((nb + NT - 1) / NT);
     if (src.np > 0)
@@ -598,6 +600,29 @@ constexpr uint64_t REDO = ~0ull;                // bucket_unique marker: take th
 constexpr uint64_t EMPTY_KEY = ~0ull;           // never a canonical k-mer for k <= 32
 constexpr uint32_t BLOCK_SPLIT_GROUP = 64;      // block tier: a larger rank group takes the splitter rank
 
+// Weighted keys (64-bit keys with 2k <= WKEY_MAX_BITS): the four bits above the k-mer hold
+// weight - 1, so one staged entry stands for 1 .. WKEY_WMAX occurrences of its k-mer (the fold pass,
+// k_fold_sc) and a key as the expansion writes it for one.  15 is the largest weight at which a u16
+// LDS count cannot overflow in any tier (the largest table holds BIG_HC = 4096 entries).  Every
+// reader of staged keys tests EMPTY_KEY first, then splits (key, weight): it hashes, compares and
+// ranks on the key alone and adds the weight where an unweighted count adds 1.  2k > 60, or a job
+// none of whose pieces was folded (BucketSrc::weighted): no weight field (wsh = 0), every weight 1 --
+// the split is then one scalar branch, not the field's arithmetic per key (it cost the unfolded
+// configs[1] wave tier 0.1 ms).
+struct WKeySpec {
+    uint64_t kmask;  // the k-mer's bits
+    int wsh;         // the weight field's shift (2k); 0: none
+};
+__device__ __host__ inline WKeySpec wkey_spec(int k, bool weighted = true) {
+    return weighted && 2 * k <= WKEY_MAX_BITS ? WKeySpec{(1ull << (2 * k)) - 1ull, 2 * k} : WKeySpec{~0ull, 0};
+}
+__device__ __forceinline__ uint64_t wkey_split(uint64_t x, const WKeySpec &ws, uint32_t &w) {
+    w = 1u;
+    if (ws.wsh == 0) return x;  // uniform
+    w += (uint32_t)(x >> ws.wsh);  // nothing lies above the field
+    return x & ws.kmask;
+}
+
 __device__ __forceinline__ uint32_t hslot(uint64_t key) {
     return (uint32_t)((key * 0x9e3779b97f4a7c15ull) >> 52) & (HSLOTS - 1);  // top 12 bits
 }
@@ -636,8 +661,11 @@ __global__ __launch_bounds__(NT) void k_bucket_count64(BucketSrc src, const Buck
     __shared__ unsigned long long s_spl[NT];  // splitter rank: sampled keys (2 KB: still 3 workgroups per CU)
     const uint32_t qi = list ? list[blockIdx.x] : blockIdx.x;  // bucket (list: the block tier only)
     const Bucket b = buckets[qi];
-    if (b.n <= skip_le) return;  // counted by the mid wave tier
+    // counted by the mid wave tier (skip_le = 0, every bucket: an empty one -- a cell without keys between
+    // two cells that each start a bucket -- must still get its bucket_unique = 0 below)
+    if (skip_le && b.n <= skip_le) return;
     const BucketView bv = bucket_view(src, b);
+    const WKeySpec ws = wkey_spec(k, src.weighted);
     if (!STREAM && (b.n > HC || b.n > small_limit)) {
         if (threadIdx.x == 0) {
             bucket_unique[qi] = REDO;
@@ -681,8 +709,9 @@ __global__ __launch_bounds__(NT) void k_bucket_count64(BucketSrc src, const Buck
         }
 #pragma unroll
         for (int q = 0; q < GB; ++q) {
-            const uint64_t key = kk[q];
-            if (key == EMPTY_KEY) continue;
+            if (kk[q] == EMPTY_KEY) continue;
+            uint32_t wt;
+            const uint64_t key = wkey_split(kk[q], ws, wt);
             // home slot: the hash's top bits (HS a power of two), else its top 32 bits scaled to HS
             uint32_t s = POW2 ? (uint32_t)((key * 0x9e3779b97f4a7c15ull) >> (64 - HBITS))
                               : (uint32_t)((((key * 0x9e3779b97f4a7c15ull) >> 32) * HS) >> 32);
@@ -691,10 +720,10 @@ __global__ __launch_bounds__(NT) void k_bucket_count64(BucketSrc src, const Buck
                 if (cur == EMPTY_KEY) cur = atomicCAS(&s_k[s], EMPTY_KEY, (unsigned long long)key);
                 if (cur == EMPTY_KEY || cur == key) {
                     const uint32_t old =
-                        atomicAdd(reinterpret_cast<uint32_t *>(&s_c[s & ~1u]), 1u << (16 * (s & 1u)));
+                        atomicAdd(reinterpret_cast<uint32_t *>(&s_c[s & ~1u]), wt << (16 * (s & 1u)));
                     if constexpr (STREAM) {
                         if (cur == EMPTY_KEY) atomicAdd(&s_nu, 1u);
-                        if (((old >> (16 * (s & 1u))) & 0xffffu) == 0xffffu) s_ovf = 1u;  // carried: give up
+                        if (((old >> (16 * (s & 1u))) & 0xffffu) + wt > 0xffffu) s_ovf = 1u;  // carried: give up
                     }
                     break;
                 }
@@ -1185,11 +1214,14 @@ __device__ __forceinline__ void wave_rank64(unsigned long long *s_gk, uint16_t *
 // (the mid tier's up to 1024 keys on the 512-key table): the count gives up -- returns ~0u, writes
 // nothing -- once more than CAP distinct keys appear (checked before each row: the table keeps
 // SL - CAP >= 64 free slots for the row's new keys).
-template <uint32_t CAP, uint32_t SL, bool ORD = true, int WKPT = WaveCfg<CAP>::KPT, int NROW = WKPT>
+// WT = false (the main wave tier of a job without a folded piece, the kernel every key of such a job
+// passes through): the weight split is compiled out -- its key mask and branch cost the unfolded
+// configs[2] load 0.4 ms per step
+template <uint32_t CAP, uint32_t SL, bool ORD = true, int WKPT = WaveCfg<CAP>::KPT, int NROW = WKPT, bool WT = true>
 __device__ __forceinline__ uint32_t wave_count_keys(WaveLds<CAP, SL> &w, uint64_t begin, uint32_t n, uint64_t lo,
                                                 int span_bits, uint64_t q, const uint64_t (&kk)[NROW],
-                                                uint64_t *__restrict__ out_keys, uint32_t *__restrict__ out_counts,
-                                                uint64_t *__restrict__ uniq) {
+                                                const WKeySpec ws, uint64_t *__restrict__ out_keys,
+                                                uint32_t *__restrict__ out_counts, uint64_t *__restrict__ uniq) {
     const int lane = threadIdx.x & 63;
     unsigned long long *s_k = w.k;
     uint16_t *s_c = w.c;
@@ -1220,15 +1252,18 @@ __device__ __forceinline__ uint32_t wave_count_keys(WaveLds<CAP, SL> &w, uint64_
     static_assert(NROW == WKPT || (NROW > WKPT && SL - CAP >= 64), "a row's new keys fit above CAP");
     uint32_t sl[NROW];
 #pragma unroll
-    for (int j = 0; j < NROW; ++j) sl[j] = wslot<SL>(kk[j]);
+    for (int j = 0; j < NROW; ++j) sl[j] = wslot<SL>(WT ? kk[j] & ws.kmask : kk[j]);
     uint32_t U = 0;
 #pragma unroll
     for (int j = 0; j < NROW; ++j) {
         bool over = false;  // uniform: more than CAP distinct keys so far (given up below)
         if constexpr (NROW > WKPT) over = U > CAP;
-        const uint64_t key = over ? EMPTY_KEY : kk[j];
+        const uint64_t x = over ? EMPTY_KEY : kk[j];
         bool fresh = false;
-        if (key != EMPTY_KEY) {
+        if (x != EMPTY_KEY) {
+            uint32_t wt = 1u;
+            uint64_t key = x;
+            if constexpr (WT) key = wkey_split(x, ws, wt);
             uint32_t s = sl[j];
             for (;;) {  // every probe a compare-and-swap
                 const unsigned long long prev = atomicCAS(&s_k[s], EMPTY_KEY, (unsigned long long)key);
@@ -1236,7 +1271,7 @@ __device__ __forceinline__ uint32_t wave_count_keys(WaveLds<CAP, SL> &w, uint64_
                 if (fresh || prev == key) break;
                 s = s + 1 == SL ? 0u : s + 1;
             }
-            atomicAdd(reinterpret_cast<uint32_t *>(&s_c[s & ~1u]), 1u << (16 * (s & 1u)));
+            atomicAdd(reinterpret_cast<uint32_t *>(&s_c[s & ~1u]), wt << (16 * (s & 1u)));
             sl[j] = s;
         }
         const uint64_t m = __ballot(fresh);
@@ -1301,22 +1336,22 @@ __device__ __forceinline__ uint32_t wave_count_keys(WaveLds<CAP, SL> &w, uint64_
 }
 
 // count one bucket (cells [c0, c1) of its bin) of <= CAP keys with the calling wave
-template <uint32_t CAP, uint32_t SL, bool ORD = true, int WKPT = WaveCfg<CAP>::KPT>
+template <uint32_t CAP, uint32_t SL, bool ORD = true, bool WT = true, int WKPT = WaveCfg<CAP>::KPT>
 __device__ __forceinline__ void wave_count_bucket(WaveLds<CAP, SL> &w, const Bucket &b, uint64_t q,
-                                                  const uint64_t (&kk)[WKPT], int k, int F,
+                                                  const uint64_t (&kk)[WKPT], int k, int F, const WKeySpec ws,
                                                   uint64_t *__restrict__ out_keys, uint32_t *__restrict__ out_counts,
                                                   uint64_t *__restrict__ bucket_unique) {
     const int sh = 2 * k - F;
     const int span_bits = b.n ? (32 - __builtin_clz(b.c1 - b.c0)) + sh : 0;
-    wave_count_keys<CAP, SL, ORD, WKPT>(w, b.begin, b.n, (uint64_t)b.c0 << sh, span_bits, q, kk, out_keys,
-                                        out_counts, bucket_unique);
+    wave_count_keys<CAP, SL, ORD, WKPT, WKPT, WT>(w, b.begin, b.n, (uint64_t)b.c0 << sh, span_bits, q, kk, ws,
+                                        out_keys, out_counts, bucket_unique);
 }
 
 // BPW buckets per wave: all their keys are loaded up front, so a wave waits
 // for HBM once per BPW buckets (waves per CU are LDS-bound).  list: bucket
 // indices (the wave tier of the buckets not counted by k_fine_sc_count), or
 // null for buckets 0..nbuckets-1.
-template <int BPW, uint32_t CAP, uint32_t SL, bool MS = false, bool ORD = true>
+template <int BPW, uint32_t CAP, uint32_t SL, bool MS = false, bool ORD = true, bool WT = true>
 __global__ __launch_bounds__(64) void k_bucket_count64_wave(BucketSrc src,
                                                             const Bucket *__restrict__ buckets, uint64_t nbuckets,
                                                             int k, uint64_t *__restrict__ out_keys,
@@ -1358,7 +1393,8 @@ __global__ __launch_bounds__(64) void k_bucket_count64_wave(BucketSrc src,
 #pragma unroll
     for (int t = 0; t < BPW; ++t)
         if (mine[t])
-            wave_count_bucket<CAP, SL, ORD>(w, b[t], qq[t], kk[t], k, src.F, out_keys, out_counts, bucket_unique);
+            wave_count_bucket<CAP, SL, ORD, WT>(w, b[t], qq[t], kk[t], k, src.F, wkey_spec(k, src.weighted), out_keys,
+                                            out_counts, bucket_unique);
 }
 
 // greedy bucket cut per bin: consecutive cells are packed while the bucket
@@ -1477,10 +1513,16 @@ hipError_t launch_bucket_count64_wave(const BucketSrc &src, const Bucket *bucket
                                       const uint32_t *list, hipStream_t s, bool ordered) {
     if (!nbuckets) return hipSuccess;
     const unsigned grid = (unsigned)((nbuckets + 1) / 2);
-#define FK_W64(MS_, ORD_)                                                                                  \
-    k_bucket_count64_wave<2, WAVE_BUCKET_CAP, WAVE_SLOTS, MS_, ORD_><<<grid, 64, 0, s>>>(src, buckets, nbuckets, k, \
-                                                                                 out_keys, out_counts,     \
-                                                                                 bucket_unique, list)
+#define FK_W64T(MS_, ORD_, WT_)                                                                                 \
+    k_bucket_count64_wave<2, WAVE_BUCKET_CAP, WAVE_SLOTS, MS_, ORD_, WT_><<<grid, 64, 0, s>>>(                 \
+        src, buckets, nbuckets, k, out_keys, out_counts, bucket_unique, list)
+#define FK_W64(MS_, ORD_)                    \
+    do {                                     \
+        if (src.weighted)                    \
+            FK_W64T(MS_, ORD_, true);        \
+        else                                 \
+            FK_W64T(MS_, ORD_, false);       \
+    } while (0)
     if (src.np > 0 && ordered)
         FK_W64(true, true);
     else if (src.np > 0)
@@ -1490,6 +1532,7 @@ hipError_t launch_bucket_count64_wave(const BucketSrc &src, const Bucket *bucket
     else
         FK_W64(false, false);
 #undef FK_W64
+#undef FK_W64T
     return hipGetLastError();
 }
 
@@ -1549,7 +1592,8 @@ __global__ __launch_bounds__(64) void k_bucket_count64_parts(BucketSrc src, cons
         return ldg_nt<uint64_t>(i < n ? pa : klast);
     };
     // 1. a sample of 64 keys, one per lane, sorted across the wave (bitonic, ascending by lane)
-    unsigned long long x = *bucket_key_ptr(v, (uint32_t)(((uint64_t)lane * n) >> 6));
+    const WKeySpec ws = wkey_spec(k, src.weighted);  // the sample, the sizes and the ranges on the k-mer alone
+    unsigned long long x = *bucket_key_ptr(v, (uint32_t)(((uint64_t)lane * n) >> 6)) & ws.kmask;
 #pragma unroll
     for (uint32_t kk = 2; kk <= 64; kk <<= 1) {
 #pragma unroll
@@ -1575,7 +1619,7 @@ __global__ __launch_bounds__(64) void k_bucket_count64_parts(BucketSrc src, cons
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         const uint32_t i = r * 64 + lane;
-        const unsigned long long key = kr[r];
+        const unsigned long long key = kr[r] & ws.kmask;
         const uint32_t g = range_of(key);
         c0 += (i < n && g == 0) ? 1u : 0u;
         c1 += (i < n && g == 1) ? 1u : 0u;
@@ -1597,8 +1641,8 @@ __global__ __launch_bounds__(64) void k_bucket_count64_parts(BucketSrc src, cons
     #pragma unroll
         for (int r = 0; r < R; ++r) {
             const uint32_t i = r * 64 + lane;
-            const unsigned long long key = kr[r];
-            const bool mine = i < n && range_of(key) == g;
+            const unsigned long long key = kr[r];  // gathered as staged (key and weight)
+            const bool mine = i < n && range_of(key & ws.kmask) == g;
             const uint64_t m = __ballot(mine);
             if (mine)
                 w.k[at + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = key;
@@ -1615,7 +1659,7 @@ __global__ __launch_bounds__(64) void k_bucket_count64_parts(BucketSrc src, cons
         const uint64_t lo = g == 0 ? klo : (g == 1 ? sp0 : sp1) + 1ull;
         const uint64_t hi = g + 1 == P ? khi : (g == 0 ? sp0 : sp1);
         const int span = hi > lo ? 64 - __builtin_clzll(hi - lo) : 0;
-        pre += wave_count_keys<CAP, SL, ORD>(w, b.begin + pre, ng, lo, span, 0, kk, out_keys, out_counts, nullptr);
+        pre += wave_count_keys<CAP, SL, ORD>(w, b.begin + pre, ng, lo, span, 0, kk, ws, out_keys, out_counts, nullptr);
     }
     if (lane == 0) bucket_unique[q] = pre;
 }
@@ -1666,7 +1710,8 @@ __global__ __launch_bounds__(64) void k_bucket_count64_mid512(BucketSrc src, con
     const int sh = 2 * k - src.F;
     const int span_bits = (32 - __builtin_clz(b.c1 - b.c0)) + sh;
     const uint32_t U = wave_count_keys<CAP, SL, ORD, WKPT, R>(w, b.begin, b.n, (uint64_t)b.c0 << sh, span_bits, q, kk,
-                                                              out_keys, out_counts, bucket_unique);
+                                                              wkey_spec(k, src.weighted), out_keys, out_counts,
+                                                              bucket_unique);
     if (U == ~0u && (threadIdx.x & 63) == 0) fb[atomicAdd(fb_count, 1u)] = q;
 }
 
@@ -1753,7 +1798,9 @@ __global__ __launch_bounds__(64) void k_bucket_split64(BucketSrc src, const Buck
                                                        uint64_t *__restrict__ skeys, SubBucket *__restrict__ subs,
                                                        SplitParent *__restrict__ parents, unsigned int *counts,
                                                        uint32_t *__restrict__ fb0, uint32_t *__restrict__ fb1,
-                                                       uint32_t block_cap, int sh, int retry) {
+                                                       uint32_t block_cap, int sh, int retry, uint64_t kmask) {
+    // kmask: the k-mer's bits of a staged key (WKeySpec) -- the sample and a key's sub-bucket go by the
+    // k-mer alone, the staged word (key and weight) is passed through to the sub-bucket
     __shared__ uint64_t s_smp[WSPL_SMAX];  // the sample, sorted; then the splitters
     __shared__ uint32_t s_cnt[WSPL_MAXS];
     const uint32_t lane = threadIdx.x;
@@ -1806,7 +1853,7 @@ __global__ __launch_bounds__(64) void k_bucket_split64(BucketSrc src, const Buck
         //    keys; the retry's half a stride later), bitonic-sorted in LDS by the wave
         const uint64_t soff = att ? (uint64_t)b.n / (2 * S) : 0;
         for (uint32_t j = lane; j < S; j += 64)
-            s_smp[j] = *bucket_key_ptr(v, (uint32_t)(((uint64_t)j * b.n) / S + soff));
+            s_smp[j] = *bucket_key_ptr(v, (uint32_t)(((uint64_t)j * b.n) / S + soff)) & kmask;
         for (uint32_t t = lane; t < WSPL_MAXS; t += 64) s_cnt[t] = 0;
         wave_lds_sync();
         for (uint32_t kk = 2; kk <= S; kk <<= 1) {
@@ -1845,7 +1892,7 @@ __global__ __launch_bounds__(64) void k_bucket_split64(BucketSrc src, const Buck
 #pragma unroll
             for (int r = 0; r < WSPL_KB; ++r)
                 if (j0 + r * 64 + lane < b.n) {
-                    const uint32_t sub = sub_of(x[r]);
+                    const uint32_t sub = sub_of(x[r] & kmask);
                     const uint32_t at = atomicAdd(&s_cnt[sub], 1u);
                     if (att == 0 && at < SPL_SLOT) skeys[sb + (uint64_t)sub * SPL_SLOT + at] = x[r];
                 }
@@ -1912,7 +1959,7 @@ __global__ __launch_bounds__(64) void k_bucket_split64(BucketSrc src, const Buck
         for (int r = 0; r < WSPL_KB; ++r) x[r] = key_at(j0 + r * 64, j0 + r * 64 + lane);
 #pragma unroll
         for (int r = 0; r < WSPL_KB; ++r)
-            if (j0 + r * 64 + lane < b.n) skeys[sb + atomicAdd(&s_cnt[sub_of(x[r])], 1u)] = x[r];
+            if (j0 + r * 64 + lane < b.n) skeys[sb + atomicAdd(&s_cnt[sub_of(x[r] & kmask)], 1u)] = x[r];
     }
 }
 
@@ -1922,7 +1969,7 @@ hipError_t launch_bucket_split64(const BucketSrc &src, const Bucket *buckets, co
                                  uint32_t *fb1, uint32_t block_cap, int k, int F, hipStream_t s, bool retry) {
     if (!(n0 + n1)) return hipSuccess;
     k_bucket_split64<<<n0 + n1, 64, 0, s>>>(src, buckets, list0, n0, list1, sbase, skeys, subs, parents, counts, fb0,
-                                            fb1, block_cap, 2 * k - F, retry ? 1 : 0);
+                                            fb1, block_cap, 2 * k - F, retry ? 1 : 0, wkey_spec(k, src.weighted).kmask);
     return hipGetLastError();
 }
 
@@ -1936,7 +1983,7 @@ __global__ __launch_bounds__(64) void k_sub_count64_seq(const Bucket *__restrict
                                                         const uint32_t *__restrict__ list,
                                                         const SplitParent *__restrict__ parents,
                                                         const SubBucket *__restrict__ subs,
-                                                        const uint64_t *__restrict__ skeys,
+                                                        const uint64_t *__restrict__ skeys, const WKeySpec ws,
                                                         uint64_t *__restrict__ out_keys,
                                                         uint32_t *__restrict__ out_counts,
                                                         uint64_t *__restrict__ bucket_unique) {
@@ -1967,8 +2014,8 @@ __global__ __launch_bounds__(64) void k_sub_count64_seq(const Bucket *__restrict
         const bool more = j + 1 < P.nsub;
         d1 = subs[P.first + (more ? j + 1 : j)];  // the last round reloads its own (unused)
         load(d1, kb);
-        pre += wave_count_keys<CAP, SL, ORD>(w, begin + pre, d0.n, d0.lo, (int)d0.span, 0, ka, out_keys, out_counts,
-                                             nullptr);
+        pre += wave_count_keys<CAP, SL, ORD>(w, begin + pre, d0.n, d0.lo, (int)d0.span, 0, ka, ws, out_keys,
+                                             out_counts, nullptr);
         if (!more) break;
         d0 = d1;  // one call site: the prefetched keys move over
 #pragma unroll
@@ -1978,14 +2025,16 @@ __global__ __launch_bounds__(64) void k_sub_count64_seq(const Bucket *__restrict
 }
 
 hipError_t launch_sub_count64_seq(const Bucket *buckets, const uint32_t *list, uint32_t nl, const SplitParent *parents,
-                                  const SubBucket *subs, const uint64_t *skeys, uint64_t *out_keys,
-                                  uint32_t *out_counts, uint64_t *bucket_unique, hipStream_t s, bool ordered) {
+                                  const SubBucket *subs, const uint64_t *skeys, int k, bool weighted,
+                                  uint64_t *out_keys, uint32_t *out_counts, uint64_t *bucket_unique, hipStream_t s,
+                                  bool ordered) {
     if (!nl) return hipSuccess;
+    const WKeySpec ws = wkey_spec(k, weighted);
     if (ordered)
-        k_sub_count64_seq<true><<<nl, 64, 0, s>>>(buckets, list, parents, subs, skeys, out_keys, out_counts,
+        k_sub_count64_seq<true><<<nl, 64, 0, s>>>(buckets, list, parents, subs, skeys, ws, out_keys, out_counts,
                                                   bucket_unique);
     else
-        k_sub_count64_seq<false><<<nl, 64, 0, s>>>(buckets, list, parents, subs, skeys, out_keys, out_counts,
+        k_sub_count64_seq<false><<<nl, 64, 0, s>>>(buckets, list, parents, subs, skeys, ws, out_keys, out_counts,
                                                    bucket_unique);
     return hipGetLastError();
 }

@@ -339,6 +339,17 @@ struct fk_ctx {
     uint64_t st_kmers = 0;                       // k-mers expanded so far
     DevBuf st_keys[STAGE_MAXP], st_cb[STAGE_MAXP], st_total, piece_starts;
     hipEvent_t st_ev[4 * STAGE_MAXP] = {};       // per piece: partition begin / end, expansion begin / end
+    // the fold of a landed piece (one rank, 64-bit keys with 2k <= 60): its duplicate k-mers become
+    // weighted keys while later pieces land (fold_piece)
+    int fold_mode = 1;                           // FASTKMER_FOLD: 0 off, 1 by the first piece's sample, 2 every eligible piece
+    uint32_t fold_wmax = WKEY_WMAX;              // FASTKMER_DEBUG_FOLD_WMAX: a lower weight cap (test hook)
+    bool fold_decided = false, fold_on = false;  // the current job's gate (mode 1: set by its first piece's sample)
+    uint64_t fold_sample_ppm = 0;                // ... entries per million sampled keys (0: no sample taken)
+    uint64_t fold_in = 0;                        // keys of the job's folded pieces
+    std::vector<uint32_t> fold_pieces;           // ... the pieces (their entries: the last word of st_cb[p])
+    DevBuf fold_cnt, fold_cb, fold_io;           // entries per cell, their scan, the sample's (keys, entries)
+    PinBuf fold_pin;                             // the folded pieces' entries (one word per piece)
+    uint64_t fold_last[4] = {0, 0, 0, 0};        // the last finished job's figures (fk_debug_fold_stats)
 
     fk::Comm *comm = nullptr;
     hipStream_t comm_stream = nullptr;

@@ -58,6 +58,7 @@ struct BucketSrc {
     const uint64_t *pk[STAGE_MAXP] = {};
     const uint64_t *pcb[STAGE_MAXP] = {};
     const struct PieceStarts *starts = nullptr;  // per bucket (launch_bucket_finish), or null
+    bool weighted = false;  // a staged piece was folded: its keys carry weights (WKeySpec)
 };
 // one bucket's keys in the staged pieces: piece p's first key at s[p] of pk[p], pre[p] keys of
 // the bucket in the pieces before p (pre[p] = ~0u for p >= np)
@@ -67,7 +68,8 @@ struct PieceStarts {
 };
 // every bucket's n / c1 (from the next bucket) and, with staged pieces (src.np > 0), its piece starts
 hipError_t launch_bucket_finish(const BucketSrc &src, struct Bucket *buckets, uint64_t nb, uint32_t nlbins,
-                                uint64_t total_keys, PieceStarts *out, hipStream_t s);
+                                const uint64_t *total_keys /* device: the cell scan's last word */, PieceStarts *out,
+                                hipStream_t s);
 
 struct Chunk {
     uint64_t rec_begin, rec_end;  // records [begin, end) of one local bin
@@ -199,6 +201,26 @@ hipError_t launch_bucket_count64(const BucketSrc &src, const Bucket *buckets, ui
 hipError_t launch_bucket_count64_big(const BucketSrc &src, const Bucket *buckets, uint64_t nlist, int k,
                                      uint64_t *out_keys, uint32_t *out_counts, uint64_t *bucket_unique,
                                      unsigned long long *oversize, const uint32_t *list, hipStream_t s);
+// weighted staged keys (64-bit keys, 2k <= WKEY_MAX_BITS): bits [2k, 2k + 4) hold weight - 1
+// (WKeySpec, fk_count_sorted.inc)
+constexpr int WKEY_MAX_BITS = 60;
+constexpr uint32_t WKEY_WMAX = 15;
+// The fold of one staged piece (64-bit keys, 2k <= WKEY_MAX_BITS; one workgroup per (bin, super-cell)
+// of 2^F2 cells): the super-cell's keys (keys, cells at cb) deduplicated in LDS and written as
+// weighted keys of weight <= wmax, in cell order, to `mid` from the super-cell's first key's offset
+// on; fcount[cell] = the cell's entries.  Cells are taken in batches of at most FOLD_HC keys; a
+// larger cell is copied through unfolded.
+constexpr uint32_t FOLD_HC = 1024;
+hipError_t launch_fold_sc(const uint64_t *keys, const uint64_t *cb, uint32_t nlbins, int k, int F, int F2,
+                          uint32_t wmax, uint64_t *mid, uint32_t *fcount, hipStream_t s);
+// count only, every `stride`-th super-cell: io[0] += keys read, io[1] += entries they fold to
+hipError_t launch_fold_sample(const uint64_t *keys, const uint64_t *cb, uint32_t nlbins, int k, int F, int F2,
+                              uint32_t wmax, uint32_t stride, unsigned long long *io, hipStream_t s);
+// after the scan of fcount into cb_new: each super-cell's entries from mid (at its raw offset, cb_raw)
+// to their dense place in keys, and the job's cell totals corrected (total[cell] -= raw - folded)
+hipError_t launch_fold_compact(const uint64_t *mid, const uint64_t *cb_raw, const uint64_t *cb_new,
+                               const uint32_t *fcount, uint32_t nlbins, int F, int F2, uint64_t *keys,
+                               uint64_t *total, hipStream_t s);
 constexpr uint32_t WAVE_BUCKET_CAP = 512;
 // table slots of a 512-key wave bucket (7.4 KB of LDS per wave, 6 waves per SIMD; 768: 5, 1.4 ms
 // slower at the configs[2] load, profiles/r05l_wave_slots_ab.txt)
@@ -274,8 +296,9 @@ hipError_t launch_bucket_split64(const BucketSrc &src, const Bucket *buckets, co
                                  SubBucket *subs, SplitParent *parents, unsigned int *counts, uint32_t *fb0,
                                  uint32_t *fb1, uint32_t block_cap, int k, int F, hipStream_t s, bool retry = false);
 hipError_t launch_sub_count64_seq(const Bucket *buckets, const uint32_t *list, uint32_t nl, const SplitParent *parents,
-                                  const SubBucket *subs, const uint64_t *skeys, uint64_t *out_keys,
-                                  uint32_t *out_counts, uint64_t *bucket_unique, hipStream_t s, bool ordered);
+                                  const SubBucket *subs, const uint64_t *skeys, int k, bool weighted,
+                                  uint64_t *out_keys, uint32_t *out_counts, uint64_t *bucket_unique, hipStream_t s,
+                                  bool ordered);
 // the same for 128-bit keys (33 <= k <= 63): sub-bucket keys as (hi, lo) word pairs, counted by the mid
 // wave tier's 512-key table; fallbacks: fb0 (<= block_cap keys, the LDS sort), fb1 (the streaming path)
 struct SubBucket128 {

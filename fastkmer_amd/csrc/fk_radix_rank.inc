@@ -8,17 +8,27 @@ __device__ __forceinline__ uint32_t digit_of(uint64_t key, int sh) { return (uin
 template <int KW>
 __device__ __forceinline__ uint32_t digit_of(u128 key, int sh) { return (uint32_t)(key >> sh) & 15u; }
 
+// the bits a bucket sort orders by: a 64-bit staged key's k-mer (WKeySpec: the weight field above it
+// is payload), every bit of a 128-bit key
+template <int KW>
+__device__ __forceinline__ typename KeyOf<KW>::T sort_kmask(int k) {
+    typedef typename KeyOf<KW>::T K;
+    if constexpr (KW == 1) return 2 * k <= WKEY_MAX_BITS ? (1ull << (2 * k)) - 1ull : ~0ull;
+    else return ~(K)0;
+}
+
 // Rank one tile of up to NT*IPT keys (blocked arrangement: thread t owns
 // items [t*IPT, t*IPT+IPT), items >= n inactive).  Returns, per item, its
 // position in the stable order by digit inside the tile; s_cnt is 16*NT u32.
 template <typename K, int IPT>
 __device__ __forceinline__ void tile_rank(const K (&key)[IPT], int n_valid_here, int sh, uint32_t *s_cnt,
                                           uint32_t *s_tmp, uint32_t (&pos)[IPT], uint32_t (&dig)[IPT],
-                                          uint32_t *digit_total /*[16] or null*/) {
+                                          uint32_t *digit_total /*[16] or null*/, uint32_t dmask = 15u) {
+    // dmask: the digit's bits that count (a weighted key's top digit stops at the k-mer's last bit)
     uint64_t lo = 0, hi = 0;  // 16 counters x 8 bits
 #pragma unroll
     for (int it = 0; it < IPT; ++it) {
-        const uint32_t d = (uint32_t)(key[it] >> sh) & 15u;
+        const uint32_t d = (uint32_t)(key[it] >> sh) & dmask;
         dig[it] = d;
         if (it < n_valid_here) {
             const int f = 8 * (d & 7);

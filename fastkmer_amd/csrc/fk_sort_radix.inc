@@ -85,7 +85,12 @@ __global__ __launch_bounds__(NT) void k_bucket_sort(BucketSrc src, const Bucket 
         kand = s_red[1][0] & s_red[1][1] & s_red[1][2] & s_red[1][3];
         __syncthreads();
     }
-    const K diff = kor ^ kand;
+    // 64-bit keys may be weighted (WKeySpec): the digits stop at the k-mer's bits (the sort is stable,
+    // so a k-mer's entries end up adjacent whatever their weights), a run's head is a change of k-mer
+    // and its count the sum of its entries' weights
+    const K kmask = sort_kmask<KW>(k);
+    const K diff = (kor ^ kand) & kmask;
+    const bool weighted = ((kor & ~kmask) != 0);  // uniform
     int lo_bit = 0, hi_bit = -1;
     if (diff != 0) {
         if constexpr (KW == 1) {
@@ -99,7 +104,7 @@ __global__ __launch_bounds__(NT) void k_bucket_sort(BucketSrc src, const Bucket 
     }
     for (int sh = lo_bit & ~3; sh <= hi_bit; sh += 4) {
         uint32_t pos[IPT], dig[IPT];
-        tile_rank<K, IPT>(key, nv, sh, s_cnt, s_tmp, pos, dig, nullptr);
+        tile_rank<K, IPT>(key, nv, sh, s_cnt, s_tmp, pos, dig, nullptr, (uint32_t)(kmask >> sh) & 15u);
 #pragma unroll
         for (int it = 0; it < IPT; ++it)
             if (it < nv) s_keys[pos[it]] = key[it];
@@ -108,7 +113,7 @@ __global__ __launch_bounds__(NT) void k_bucket_sort(BucketSrc src, const Bucket 
         for (int it = 0; it < IPT; ++it) key[it] = (it < nv) ? s_keys[my0 + it] : ~(K)0;
         __syncthreads();
     }
-    if (hi_bit < 0) {
+    if (hi_bit < 0 && !weighted) {
         // all keys equal
         if (threadIdx.x == 0) {
             store_key(out_keys, b.begin, key[0]);
@@ -125,7 +130,7 @@ __global__ __launch_bounds__(NT) void k_bucket_sort(BucketSrc src, const Bucket 
 #pragma unroll
     for (int it = 0; it < IPT; ++it) {
         const int i = my0 + it;
-        if (i < n && (i == 0 || s_keys[i - 1] != key[it])) heads |= 1u << it;
+        if (i < n && (i == 0 || ((s_keys[i - 1] ^ key[it]) & kmask) != 0)) heads |= 1u << it;
     }
     uint32_t nu;
     uint32_t u = block_excl_sum<uint32_t>((uint32_t)__popc(heads), s_tmp, &nu);
@@ -136,8 +141,13 @@ __global__ __launch_bounds__(NT) void k_bucket_sort(BucketSrc src, const Bucket 
     __syncthreads();
     for (uint32_t q = threadIdx.x; q < nu; q += NT) {
         const uint32_t hp = s_cnt[q];
-        store_key(out_keys, b.begin + q, s_keys[hp]);
-        out_counts[b.begin + q] = s_cnt[q + 1] - hp;
+        store_key(out_keys, b.begin + q, s_keys[hp] & kmask);
+        uint32_t cnt = s_cnt[q + 1] - hp;
+        if constexpr (KW == 1) {
+            if (weighted)  // the run's weights (weight - 1 above the k-mer) on top of its length
+                for (uint32_t j = hp, e = hp + cnt; j < e; ++j) cnt += (uint32_t)(s_keys[j] >> (2 * k));
+        }
+        out_counts[b.begin + q] = cnt;
     }
     if (threadIdx.x == 0) bucket_unique[qi] = nu;
 }
@@ -181,7 +191,7 @@ __global__ __launch_bounds__(NT) void k_bucket_sort_large(BucketSrc src, const B
     __shared__ uint64_t s_hist[16];
     __shared__ K s_red[2][NT / 64];
     __shared__ K s_carry;
-    __shared__ uint64_t s_state[2];
+    __shared__ uint64_t s_state[3];
     __shared__ uint64_t s_soff;
 
     const uint32_t qi = list ? list[blockIdx.x] : blockIdx.x;
@@ -233,7 +243,11 @@ __global__ __launch_bounds__(NT) void k_bucket_sort_large(BucketSrc src, const B
         kand = s_red[1][0] & s_red[1][1] & s_red[1][2] & s_red[1][3];
         __syncthreads();
     }
-    const K diff = kor ^ kand;
+    // weighted 64-bit keys as in k_bucket_sort: digits up to the k-mer's last bit, heads by k-mer,
+    // counts by weight
+    const K kmask = sort_kmask<KW>(k);
+    const int wsh = KW == 1 && 2 * k <= WKEY_MAX_BITS ? 2 * k : 0;  // 0: no weight field
+    const K diff = (kor ^ kand) & kmask;
     int lo_bit = 0, hi_bit = -1;
     if (diff != 0) {
         if constexpr (KW == 1) {
@@ -246,13 +260,14 @@ __global__ __launch_bounds__(NT) void k_bucket_sort_large(BucketSrc src, const B
         }
     }
     for (int sh = lo_bit & ~3; sh <= hi_bit; sh += 4) {
+        const uint32_t dmask = (uint32_t)(kmask >> sh) & 15u;
         // digit histogram of the whole bucket
         if (threadIdx.x < 16) s_hist[threadIdx.x] = 0;
         __syncthreads();
         for (uint64_t i = threadIdx.x; i < n; i += NT) {
             K x;
             load_key(bufA, offA + i, x);
-            atomicAdd((unsigned long long *)&s_hist[(uint32_t)(x >> sh) & 15u], 1ull);
+            atomicAdd((unsigned long long *)&s_hist[(uint32_t)(x >> sh) & dmask], 1ull);
         }
         __syncthreads();
         if (threadIdx.x == 0) {
@@ -275,7 +290,7 @@ __global__ __launch_bounds__(NT) void k_bucket_sort_large(BucketSrc src, const B
                     key[it] = ~(K)0;
             }
             uint32_t pos[IPT], dig[IPT];
-            tile_rank<K, IPT>(key, nv, sh, s_cnt, s_tmp, pos, dig, s_dtot);
+            tile_rank<K, IPT>(key, nv, sh, s_cnt, s_tmp, pos, dig, s_dtot, dmask);
             // pos = position in the tile's digit order; digit d starts at s_cnt[d*NT]
 #pragma unroll
             for (int it = 0; it < IPT; ++it) {
@@ -300,9 +315,11 @@ __global__ __launch_bounds__(NT) void k_bucket_sort_large(BucketSrc src, const B
     // run-length encode bufA -> out_keys/out_counts.  When bufA == out_keys
     // this compacts in place: a tile is read into registers before any
     // write, and unique index <= position, so later tiles are never clobbered.
+    // Counts are differences of the weight before a head (an unweighted key weighs 1: its position)
     if (threadIdx.x == 0) {
         s_state[0] = 0;      // unique keys written so far
-        s_state[1] = ~0ull;  // position of the head whose count is still open
+        s_state[1] = ~0ull;  // weight before the head whose count is still open
+        s_state[2] = 0;      // weight before this tile
     }
     __syncthreads();
     for (uint64_t t0 = 0; t0 < n; t0 += TILE) {
@@ -324,47 +341,59 @@ __global__ __launch_bounds__(NT) void k_bucket_sort_large(BucketSrc src, const B
             load_key(bufA, offA + my0 - 1, pk);
         else
             pk = ~(K)0;
-        uint32_t heads = 0;
+        uint32_t heads = 0, wsum = 0;
+        uint32_t wt[IPT];
 #pragma unroll
         for (int it = 0; it < IPT; ++it) {
-            if (it < nv && ((my0 + it) == 0 || key[it] != pk)) heads |= 1u << it;
+            if (it < nv && ((my0 + it) == 0 || ((key[it] ^ pk) & kmask) != 0)) heads |= 1u << it;
             pk = key[it];
+            wt[it] = it < nv ? 1u : 0u;
+            if constexpr (KW == 1)
+                if (wsh && it < nv) wt[it] += (uint32_t)(key[it] >> wsh);
+            wsum += wt[it];
         }
         __syncthreads();  // every read of this tile (and of s_carry) is done
 #pragma unroll
         for (int it = 0; it < IPT; ++it)
             if ((uint64_t)it + my0 == t0 + tlen - 1) s_carry = key[it];
-        uint32_t nh;
+        uint32_t nh, wtile;
         uint32_t u = block_excl_sum<uint32_t>((uint32_t)__popc(heads), s_tmp, &nh);
+        uint32_t wpre = block_excl_sum<uint32_t>(wsum, s_tmp, &wtile);  // the tile's weight before this thread's keys
         const uint64_t ubase = s_state[0];
         const uint64_t open_head = s_state[1];
+        const uint64_t w0 = s_state[2];
         const uint32_t u0 = u;
 #pragma unroll
-        for (int it = 0; it < IPT; ++it)
-            if ((heads >> it) & 1u) s_cnt[u++] = (uint32_t)(threadIdx.x * IPT + it);
-        if (threadIdx.x == 0) s_cnt[nh] = (uint32_t)tlen;
+        for (int it = 0; it < IPT; ++it) {
+            if ((heads >> it) & 1u) s_cnt[u++] = wpre;
+            wpre += wt[it];
+        }
+        if (threadIdx.x == 0) s_cnt[nh] = wtile;
         __syncthreads();
         if (nh > 0 && threadIdx.x == 0 && open_head != ~0ull)  // close the run left open by the previous tile
-            out_counts[b.begin + ubase - 1] = (uint32_t)(t0 + s_cnt[0] - open_head);
+            out_counts[b.begin + ubase - 1] = (uint32_t)(w0 + s_cnt[0] - open_head);
         u = u0;
 #pragma unroll
         for (int it = 0; it < IPT; ++it) {
             if ((heads >> it) & 1u) {
-                store_key(out_keys, b.begin + ubase + u, key[it]);
+                store_key(out_keys, b.begin + ubase + u, key[it] & kmask);
                 if (u + 1 < nh) out_counts[b.begin + ubase + u] = s_cnt[u + 1] - s_cnt[u];
                 ++u;
             }
         }
         __syncthreads();
-        if (threadIdx.x == 0 && nh > 0) {
-            s_state[0] = ubase + nh;
-            s_state[1] = t0 + s_cnt[nh - 1];
+        if (threadIdx.x == 0) {
+            if (nh > 0) {
+                s_state[0] = ubase + nh;
+                s_state[1] = w0 + s_cnt[nh - 1];
+            }
+            s_state[2] = w0 + wtile;
         }
         __syncthreads();
     }
     if (threadIdx.x == 0) {
         const uint64_t ub = s_state[0];
-        if (ub > 0) out_counts[b.begin + ub - 1] = (uint32_t)(n - s_state[1]);
+        if (ub > 0) out_counts[b.begin + ub - 1] = (uint32_t)(s_state[2] - s_state[1]);
         bucket_unique[qi] = ub;
     }
 }

@@ -91,7 +91,9 @@ typedef struct fk_stats {
     double ms_exchange_tail;   /* fk_finish: the last piece posted -> every rank's records received */
     /* pieces counted while later ones were still being copied in / received (sorted count) */
     uint64_t pieces_counted;   /* staged pieces of the last fk_finish (0: one count of the whole input) */
-    uint64_t heavy_keys;       /* sorted count: k-mers in the buckets above the wave tier (split or block / big) */
+    uint64_t heavy_keys;       /* sorted count: k-mers in the buckets above the wave tier (split or block / big);
+                                  with folded pieces (fk_debug_fold_stats) this and the buckets' sizes count
+                                  staged entries, a folded entry standing for up to 15 occurrences */
     uint64_t block_buckets;    /* block tier: buckets above the wave tier (k <= 32: 512 keys, k > 32: 256) counted by
                                   the mid wave tier, one wave each: up to 1024 keys (k <= 32) / 512 keys (k > 32) */
     uint64_t big_buckets;      /* above the block tier: split into wave-sized sub-buckets (k_bucket_split64 /
@@ -566,6 +568,19 @@ size_t fk_read_stats_scratch_bytes(size_t n_bases);
 int fk_debug_wave_count(int32_t device, int32_t k, int32_t F, uint32_t c0, uint32_t c1, int32_t slots,
                         const uint64_t *keys, uint32_t n, uint64_t *out_keys, uint32_t *out_counts,
                         uint32_t *n_out);
+/* The same for a bucket of weighted keys, as the fold of a landed piece leaves
+ * them (2k <= 60: bits [2k, 2k + 4) of a key hold weight - 1, the key stands
+ * for 1..15 occurrences of its k-mer): the counts are sums of weights.  A key
+ * with bits above its k-mer where there is no weight field (k = 31), or above
+ * the field, is rejected (FK_E_RANGE). */
+int fk_debug_wave_count_w(int32_t device, int32_t k, int32_t F, uint32_t c0, uint32_t c1, int32_t slots,
+                          const uint64_t *keys, uint32_t n, uint64_t *out_keys, uint32_t *out_counts,
+                          uint32_t *n_out);
+/* The fold of the last fk_finish (one rank's staged pieces, k <= 30; FASTKMER_FOLD
+ * = 0 off, 1 by a sample of the first piece, 2 every eligible piece): out[0] =
+ * pieces folded, out[1] = their k-mers, out[2] = the weighted entries they were
+ * folded to, out[3] = the sample's entries per million k-mers (0: no sample). */
+int fk_debug_fold_stats(const fk_ctx *ctx, uint64_t out[4]);
 
 /* ---- test hooks of the failure semantics (no reference counterpart) ----
  * fk_debug_comm_hold queues, on every stream the context's collectives run on,
