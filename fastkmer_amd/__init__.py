@@ -205,6 +205,9 @@ def lib():
         "fk_debug_wave_count_w": (ctypes.c_int, [I32, I32, I32, ctypes.c_uint32, ctypes.c_uint32, I32, P,
                                                  ctypes.c_uint32, P, P, P]),
         "fk_debug_fold_stats": (ctypes.c_int, [P, P]),
+        "fk_debug_count_pieces": (ctypes.c_int, [P, I32, I32, P, P, I32, ctypes.c_uint32]),
+        "fk_debug_tier_stats": (ctypes.c_int, [P, P]),
+        "fk_debug_staged_piece": (ctypes.c_int, [P, I32, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -896,6 +899,45 @@ class KmerCounter:
         _check(lib().fk_debug_fold_stats(self._h, out))
         return {"pieces_folded": int(out[0]), "entries_in": int(out[1]), "entries_out": int(out[2]),
                 "sample_ratio": int(out[3]) / 1e6 if out[3] else None}
+
+    def debug_count_pieces(self, F: int, keys, cell_counts, weighted: bool = False, fold_mask: int = 0) -> None:
+        """Test hook (fk_debug_count_pieces): the staged count over the caller's pieces.  keys[p]:
+        piece p's keys by (bin, cell) (uint64; (hi, lo) rows for k > 32), cell_counts[p]: its keys per
+        cell (num_bins << F).  weighted: keys hold weight - 1 in bits [2k, 2k + 4); fold_mask: the
+        pieces folded first.  Afterwards the counter is as after finish()."""
+        kw = 1 if self.k <= 32 else 2
+        ks = [np.ascontiguousarray(a, dtype=np.uint64).reshape(-1) for a in keys]
+        cs = [np.ascontiguousarray(a, dtype=np.uint64).reshape(-1) for a in cell_counts]
+        if len(ks) != len(cs):
+            raise ValueError("one cell_counts array per piece")
+        for a, n in zip(ks, cs):
+            if n.size != self.num_bins << F or a.size != int(n.sum()) * kw:
+                raise ValueError("a piece holds sum(cell_counts) keys in num_bins << F cells")
+        ka = (ctypes.c_void_p * max(len(ks), 1))(*[a.ctypes.data for a in ks])
+        ca = (ctypes.c_void_p * max(len(cs), 1))(*[a.ctypes.data for a in cs])
+        self._sizes = None
+        _check(lib().fk_debug_count_pieces(self._h, F, len(ks), ka, ca, int(bool(weighted)), fold_mask))
+
+    def debug_tier_stats(self) -> dict:
+        """Test hook (fk_debug_tier_stats): the last tiered count's census -- mid-tier buckets handed
+        on to the 1024-key kernel, the split's fallbacks of at most / above 2048 keys, the buckets on
+        the streaming path, and the mid tier's first kernel (None, "ranges" or "whole")."""
+        out = (ctypes.c_uint64 * 8)()
+        _check(lib().fk_debug_tier_stats(self._h, out))
+        return {"nmidfb": int(out[0]), "nfbB": int(out[1]), "nfbG": int(out[2]), "nlarge": int(out[3]),
+                "mid_mode": (None, "ranges", "whole")[int(out[4])]}
+
+    def debug_staged_piece(self, p: int):
+        """Test hook (fk_debug_staged_piece): (keys, cell offsets) of staged piece p of the last
+        counted job as the count read it (after its fold, if any); the offsets cover
+        num_bins << stats()["fine_bits"] cells."""
+        kw = 1 if self.k <= 32 else 2
+        cb = np.zeros((self.num_bins << self.stats()["fine_bits"]) + 1, dtype=np.uint64)
+        _check(lib().fk_debug_staged_piece(self._h, p, None, cb.ctypes.data))
+        keys = np.zeros(max(int(cb[-1]), 1) * kw, dtype=np.uint64)
+        _check(lib().fk_debug_staged_piece(self._h, p, keys.ctypes.data, cb.ctypes.data))
+        keys = keys[:int(cb[-1]) * kw]
+        return (keys if kw == 1 else keys.reshape(-1, 2)), cb
 
 
 def debug_wave_count(keys: np.ndarray, k: int, F: int, c0: int, c1: int, slots: int, device: int = 0,

@@ -1464,7 +1464,7 @@ static bool staged_ok(const fk_ctx *c) {
     return c->cfg.k <= 63 && !c->force_large;
 }
 
-static SortedPlan sorted_plan(const fk_ctx *c, uint64_t max_bin_kmers) {
+static SortedPlan sorted_plan(const fk_ctx *c, uint64_t max_bin_kmers, int force_F = 0) {
     SortedPlan pl;
     const int k = c->cfg.k;
     const uint32_t cap = 2048;  // keys per LDS bucket (k_bucket_count64 / 128-bit k_bucket_sort)
@@ -1486,6 +1486,7 @@ static SortedPlan sorted_plan(const fk_ctx *c, uint64_t max_bin_kmers) {
     while (F < MAX_FINE_BITS && ((uint64_t)1 << F) * target < max_bin_kmers) ++F;
     if (!two_level) F = std::min(F, MAX_FINE_BITS - 1);  // one-level scatter: 8 << F bytes of LDS <= 128 KB
     F = std::min(F, 2 * k);
+    if (force_F) F = force_F;  // fk_debug_count_pieces: the caller's cells, everything else as the product's
     // k <= 63: two levels (super-cells, then cells; one level measured slower, DESIGN.md §4 "Count" 7);
     // cells per super-cell: 2^5 up to F = 13, 2^6 above (measured at configs[1] and at 8x larger bins)
     const uint32_t wave_cap = c->KW == 1 ? WAVE_BUCKET_CAP : WAVE128_BUCKET_CAP;
@@ -1609,6 +1610,7 @@ struct BucketCount {
     // what the 64-bit mid tier's first kernel and the split leave: the buckets for the 1024-key kernel
     // (mid_fb), for the block path (fbB) and for the big-table / streaming path (fbG)
     bool mid_wave = false;
+    int mid_mode = 0;  // the mid tier's first kernel: 0 none, 1 key ranges, 2 whole buckets (fk_debug_tier_stats)
     uint32_t *mid_fb = nullptr, *fbB = nullptr, *fbG = nullptr;
     uint32_t nmidfb = 0, nfbB = 0, nfbG = 0;
 
@@ -1715,6 +1717,7 @@ static int bucket_cut(BucketCount &t, const SortedPlan &pl, uint64_t total_kmers
     c->stats.fine_bits = (uint64_t)F;
     c->stats.heavy_keys = 0;
     c->stats.split_buckets = c->stats.sub_buckets = 0;
+    std::fill(c->tier_last, c->tier_last + 8, 0ull);
     return FK_OK;
 }
 
@@ -1771,6 +1774,7 @@ static int mid_tier_first(BucketCount &t) {
     const bool parts = c->mid_parts == 1 || (c->mid_parts != 2 && t.ntier[0] >= MID_PARTS_MIN);
     FK_TRY(ensure(c->mid_fb, (uint64_t)t.ntier[0] * 4));
     t.mid_fb = c->mid_fb.as<uint32_t>();
+    t.mid_mode = parts ? 1 : 2;
     if (parts)
         HIP_TRY(launch_bucket_count64_parts(t.src, t.buckets(), t.lists, t.ntier[0], t.k, t.out_keys(), t.out_counts(),
                                             t.unique(), t.mid_fb, t.mid_fb_count(), t.heavy.s, t.ordered));
@@ -1924,6 +1928,7 @@ static int whole_bucket_tier(BucketCount &t, uint64_t total_kmers) {
     HIP_TRY(hipMemcpyAsync(&oversize, c->misc.p, 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     c->stats.oversize_buckets = oversize;
+    c->tier_last[3] = oversize;
     if (oversize) {
         FK_TRY(ensure(c->scratch, total_kmers * 8 * c->KW));
         HIP_TRY(launch_bucket_sort_large(c->KW, t.src, t.buckets(), t.nbuckets, t.k, c->scratch.as<uint64_t>(),
@@ -1955,6 +1960,9 @@ static int sorted_count_buckets(fk_ctx *c, StreamWs on, hipStream_t cut, const S
     HIP_TRY(hipEventRecord(c->side_ev[1], t.heavy.s));
     HIP_TRY(hipStreamWaitEvent(t.s.s, c->side_ev[1], 0));
     c->stats.oversize_buckets = nlarge;
+    // the census of this count (fk_debug_tier_stats): figures the steps above read to the host anyway
+    c->tier_last[0] = t.nmidfb, c->tier_last[1] = t.nfbB, c->tier_last[2] = t.nfbG, c->tier_last[3] = nlarge;
+    c->tier_last[4] = (uint64_t)t.mid_mode;
     return FK_OK;
 }
 
@@ -2281,6 +2289,7 @@ static void pieces_reset(fk_ctx *c) {
     c->fold_sample_ppm = 0;
     c->fold_in = 0;
     c->fold_pieces.clear();
+    c->st_weighted = false;
 }
 
 // Staged pieces per job: 128-bit keys at most STAGE_MAXP128 (their kernels' piece loops stop there)
@@ -2367,7 +2376,8 @@ static int staged_count(fk_ctx *c, hipStream_t cut) {
                               c->cell_base.as<uint64_t>() + ncell_all, *on.ws, cs));
     BucketSrc src{nullptr, pl.F};
     src.np = (int)c->st_np;
-    src.weighted = !c->fold_pieces.empty();
+    src.weighted = !c->fold_pieces.empty() || c->st_weighted;
+    c->last_np = c->st_np, c->last_cells = ncell_all;
     for (uint32_t p = 0; p < c->st_np; ++p) {
         src.pk[p] = c->st_keys[p].as<uint64_t>();
         src.pcb[p] = c->st_cb[p].as<uint64_t>();
@@ -3248,6 +3258,129 @@ FK_EXPORT int fk_debug_wave_count_w(int32_t device, int32_t k, int32_t F, uint32
 FK_EXPORT int fk_debug_fold_stats(const fk_ctx *c, uint64_t out[4]) {
     if (!c || !out) return set_err(FK_E_INVALID, "null argument");
     std::copy(c->fold_last, c->fold_last + 4, out);
+    return FK_OK;
+}
+
+// ---------------------------------------------------------------------------
+// test hooks: the staged count (the bucket cut, every tier, the fold) over caller-supplied pieces
+// ---------------------------------------------------------------------------
+// Nothing of the count is reimplemented: the context is filled the way staged_expand_chunks fills it
+// (st_keys, st_cb, st_total, st_plan, st_np, st_kmers), then fold_piece and staged_count run as they
+// do in a job, and the context is left as fk_finish leaves it.
+FK_EXPORT int fk_debug_count_pieces(fk_ctx *c, int32_t F, int32_t np, const uint64_t *const *keys,
+                                    const uint64_t *const *cell_counts, int32_t weighted, uint32_t fold_mask) {
+    if (!c || !keys || !cell_counts) return set_err(FK_E_INVALID, "null argument");
+    const int k = c->cfg.k, KW = c->KW;
+    if (!staged_eligible(c)) return set_err(FK_E_INVALID, "staged pieces need k <= 63, one rank and no communicator");
+    if (c->job_open) return set_err(FK_E_STATE, "fk_debug_count_pieces inside a job (after its first fk_ingest)");
+    if (F < 1 || F > std::min(MAX_FINE_BITS, 2 * k)) return set_err(FK_E_INVALID, "F = %d outside 1 .. min(%d, 2k)", F, MAX_FINE_BITS);
+    if (np < 1 || (uint32_t)np > stage_maxp(c)) return set_err(FK_E_INVALID, "%d pieces: 1 .. %u", np, stage_maxp(c));
+    const bool wfield = KW == 1 && 2 * k <= WKEY_MAX_BITS;
+    if ((weighted || fold_mask) && !wfield)
+        return set_err(FK_E_INVALID, "k = %d: no weight field (weighted keys and the fold need 2k <= %d)", k, WKEY_MAX_BITS);
+    if (fold_mask >> np) return set_err(FK_E_INVALID, "fold_mask names a piece past the %d given", np);
+    for (int p = 0; p < np; ++p)
+        if (!keys[p] || !cell_counts[p]) return set_err(FK_E_INVALID, "null piece %d", p);
+    // every key in the cell and bin its position says, nothing above the k-mer but a weight, no EMPTY_KEY
+    // (~0: at k = 30 the all-T k-mer under weight 15 -- canonical k-mers are never all T, and the weight
+    // field stops at 14 + 1)
+    const uint32_t nlb = c->nlb;
+    const uint64_t ncell_all = (uint64_t)nlb << F;
+    const int sh = 2 * k - F;
+    std::vector<std::vector<uint64_t>> cb((size_t)np);
+    std::vector<uint64_t> total(ncell_all, 0);
+    uint64_t sumw = 0, entries = 0;
+    for (int p = 0; p < np; ++p) {
+        uint64_t maxw = 1;
+        cb[p].assign(ncell_all + 1, 0);
+        for (uint64_t g = 0; g < ncell_all; ++g) {
+            const uint64_t n = cell_counts[p][g];
+            if (n >= (1ull << 32)) return set_err(FK_E_RANGE, "piece %d, cell %llu: %llu keys", p, (unsigned long long)g, (unsigned long long)n);
+            cb[p][g + 1] = cb[p][g] + n;
+            total[g] += n;
+            const int32_t bin = global_bin(c, (uint32_t)(g >> F));
+            const uint64_t cell = g & ((1ull << F) - 1);
+            for (uint64_t i = cb[p][g]; i < cb[p][g + 1]; ++i) {
+                KmerKey f = KW == 1 ? KmerKey{0, keys[p][i]} : KmerKey{keys[p][2 * i], keys[p][2 * i + 1]};
+                uint64_t w = 1;
+                if (KW == 1 && f.lo == ~0ull) return set_err(FK_E_RANGE, "piece %d, key %llu is EMPTY_KEY", p, (unsigned long long)i);
+                if (weighted) {
+                    w += f.lo >> (2 * k);
+                    if (w > WKEY_WMAX) return set_err(FK_E_RANGE, "piece %d, key %llu: bits above the weight field", p, (unsigned long long)i);
+                    f.lo &= (1ull << (2 * k)) - 1ull;
+                }
+                if (!key_is_kmer(f, k)) return set_err(FK_E_RANGE, "piece %d, key %llu: bits above the k-mer", p, (unsigned long long)i);
+                const uint64_t kc = sh >= 64 ? (f.hi >> (sh - 64)) : (sh == 0 ? f.lo : ((KW == 2 ? f.hi << (64 - sh) : 0ull) | (f.lo >> sh)));
+                if (kc != cell) return set_err(FK_E_RANGE, "piece %d, key %llu lies in cell %llu, not %llu", p, (unsigned long long)i, (unsigned long long)kc, (unsigned long long)cell);
+                const uint32_t sig = KW == 2 ? kmer_signature<true>(f, revcomp_key<true>(f, k), k, c->cfg.m)
+                                             : kmer_signature<false>(f, revcomp_key<false>(f, k), k, c->cfg.m);
+                if ((int32_t)bin_of_signature(sig, c->fm) != bin)
+                    return set_err(FK_E_RANGE, "piece %d, key %llu belongs to bin %d, not %d", p, (unsigned long long)i, (int32_t)bin_of_signature(sig, c->fm), bin);
+                sumw += w;
+                maxw = std::max(maxw, w);
+            }
+        }
+        // a k-mer of multiplicity m folds to ceil(m / wmax) entries: at most the piece's keys (the room the
+        // fold has, as in a job, whose pieces arrive unweighted) only while no weight exceeds wmax
+        if ((fold_mask >> p & 1u) && maxw > c->fold_wmax)
+            return set_err(FK_E_INVALID, "piece %d holds weight %llu above the fold's cap %u: the fold would grow it", p,
+                           (unsigned long long)maxw, c->fold_wmax);
+        entries += cb[p][ncell_all];
+    }
+    if (entries == 0) return set_err(FK_E_INVALID, "no keys");
+    DeviceGuard dg_(c->device);
+    const StreamWs on = c->main_on();
+    hipStream_t s = on.s;
+    HIP_TRY(hipStreamSynchronize(s));
+    // a new job without input: what map_records resets
+    reset_results(c);
+    c->stats = fk_stats{};
+    c->nrec = 0;
+    c->rec_tiled = false;
+    pieces_reset(c);
+    c->nkmers = sumw;
+    c->stats.kmers = sumw;
+    c->st_plan = sorted_plan(c, entries, F);
+    if (!c->st_plan.tiered || !c->st_plan.two_level) return set_err(FK_E_STATE, "staged pieces need the tiered two-level count");
+    uint64_t maxp = 0;
+    for (int p = 0; p < np; ++p) {
+        const uint64_t n = cb[p][ncell_all];
+        maxp = std::max(maxp, n);
+        FK_TRY(ensure(c->st_keys[p], std::max<uint64_t>(n, 1) * 8 * KW));
+        FK_TRY(ensure(c->st_cb[p], (ncell_all + 1) * 8));
+        if (n) HIP_TRY(hipMemcpy(c->st_keys[p].p, keys[p], n * 8 * KW, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c->st_cb[p].p, cb[p].data(), (ncell_all + 1) * 8, hipMemcpyHostToDevice));
+    }
+    FK_TRY(ensure(c->st_total, ncell_all * 8));
+    HIP_TRY(hipMemcpy(c->st_total.p, total.data(), ncell_all * 8, hipMemcpyHostToDevice));
+    c->st_np = (uint32_t)np;
+    c->st_kmers = entries;
+    c->st_weighted = weighted != 0;
+    int rc = FK_OK;
+    if (fold_mask) rc = ensure(c->mid, maxp * 8);  // the fold's scratch: in a job, the piece's first expansion level
+    for (int p = 0; p < np && rc == FK_OK; ++p)
+        if (fold_mask >> p & 1u) rc = fold_piece(c, on, (uint32_t)p, cb[p][ncell_all]);
+    if (rc == FK_OK) rc = staged_count(c, nullptr);
+    if (rc == FK_OK) fold_report(c, true);
+    pieces_reset(c);
+    return rc;
+}
+
+FK_EXPORT int fk_debug_tier_stats(const fk_ctx *c, uint64_t out[8]) {
+    if (!c || !out) return set_err(FK_E_INVALID, "null argument");
+    std::copy(c->tier_last, c->tier_last + 8, out);
+    return FK_OK;
+}
+
+FK_EXPORT int fk_debug_staged_piece(fk_ctx *c, int32_t p, uint64_t *out_keys, uint64_t *out_cb) {
+    if (!c || !out_cb) return set_err(FK_E_INVALID, "null argument");
+    if (!c->have_result || p < 0 || (uint32_t)p >= c->last_np)
+        return set_err(FK_E_STATE, "piece %d: the last job counted %u staged pieces", p, c->have_result ? c->last_np : 0u);
+    DeviceGuard dg_(c->device);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(out_cb, c->st_cb[p].p, (c->last_cells + 1) * 8, hipMemcpyDeviceToHost));
+    const uint64_t n = out_cb[c->last_cells];
+    if (out_keys && n) HIP_TRY(hipMemcpy(out_keys, c->st_keys[p].p, n * 8 * c->KW, hipMemcpyDeviceToHost));
     return FK_OK;
 }
 

@@ -350,6 +350,14 @@ struct fk_ctx {
     DevBuf fold_cnt, fold_cb, fold_io;           // entries per cell, their scan, the sample's (keys, entries)
     PinBuf fold_pin;                             // the folded pieces' entries (one word per piece)
     uint64_t fold_last[4] = {0, 0, 0, 0};        // the last finished job's figures (fk_debug_fold_stats)
+    // test hooks of the staged count (fk_debug_count_pieces, fk_debug_tier_stats, fk_debug_staged_piece)
+    bool st_weighted = false;                    // the current job's pieces hold weighted keys as given (no fold ran)
+    // the last tiered count's census, from the figures its driver read anyway: [0] mid-tier buckets handed
+    // on, [1] / [2] split fallbacks of at most / above cap keys, [3] buckets on the streaming path,
+    // [4] the mid tier's first kernel (0 none, 1 key ranges, 2 whole on the 512-key table)
+    uint64_t tier_last[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint32_t last_np = 0;                        // the last staged count's pieces and cells (fk_debug_staged_piece)
+    uint64_t last_cells = 0;
 
     fk::Comm *comm = nullptr;
     hipStream_t comm_stream = nullptr;

@@ -581,6 +581,34 @@ int fk_debug_wave_count_w(int32_t device, int32_t k, int32_t F, uint32_t c0, uin
  * pieces folded, out[1] = their k-mers, out[2] = the weighted entries they were
  * folded to, out[3] = the sample's entries per million k-mers (0: no sample). */
 int fk_debug_fold_stats(const fk_ctx *ctx, uint64_t out[4]);
+/* The staged count -- the bucket cut, every tier and its fallbacks, the fold -- over
+ * staged pieces the caller supplies, on a context created as usual (k <= 63, one
+ * rank, no communicator, no job open).  F = cell bits, 1 .. min(15, 2k); the
+ * super-cell bits follow from F as in a job.  np = 1 .. 5 pieces (k > 32: 1 .. 4).
+ * keys[p] (host) = piece p's keys laid out by (local bin, cell): one word for
+ * k <= 32, (hi, lo) pairs above; cell_counts[p] = its keys per cell, bins << F
+ * words.  weighted (2k <= 60 only): bits [2k, 2k + 4) of a key hold weight - 1
+ * <= 14.  Every piece whose bit is set in fold_mask (2k <= 60 only) is folded first
+ * by the job's own fold, under FASTKMER_DEBUG_FOLD_WMAX.  Every key must lie in the
+ * cell and the bin its position says and have nothing above its k-mer but the
+ * weight (FK_E_RANGE); the word ~0 is refused too: it marks an empty table slot,
+ * and is a k-mer only at k = 32 (all T) or, under weight 15, at k = 30 (all T) --
+ * canonical k-mers are never all T.  Afterwards the context is as fk_finish leaves
+ * it: fk_bin_sizes, fk_get_bin, fk_get_stats (kmers = the sum of the weights),
+ * fk_debug_fold_stats work, and so does a following job. */
+int fk_debug_count_pieces(fk_ctx *ctx, int32_t F, int32_t np, const uint64_t *const *keys,
+                          const uint64_t *const *cell_counts, int32_t weighted, uint32_t fold_mask);
+/* The last tiered count's census, from figures its driver reads anyway: out[0] =
+ * mid-tier buckets (513 .. 1024 keys, k <= 32) its first kernel handed on to the
+ * 1024-key kernel, out[1] / out[2] = split buckets left to the block kernel / LDS
+ * sort (at most 2048 keys) and to the big table or the streaming path (above),
+ * out[3] = buckets that ended on the streaming path, out[4] = the mid tier's first
+ * kernel (0 none, 1 key ranges, 2 whole buckets on the 512-key table); out[5..8) = 0. */
+int fk_debug_tier_stats(const fk_ctx *ctx, uint64_t out[8]);
+/* Staged piece p of the last counted job as the count read it (folded, if it was):
+ * out_cb = the exclusive scan of its keys per cell, (bins << F) + 1 words, the last
+ * one the piece's keys; out_keys (or NULL) = those keys.  Valid until the next job. */
+int fk_debug_staged_piece(fk_ctx *ctx, int32_t p, uint64_t *out_keys, uint64_t *out_cb);
 
 /* ---- test hooks of the failure semantics (no reference counterpart) ----
  * fk_debug_comm_hold queues, on every stream the context's collectives run on,

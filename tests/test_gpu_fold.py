@@ -138,13 +138,40 @@ def test_weight_cap(forced, monkeypatch, wmax):
     assert_same_as_oracle(kc, ref)
 
 
-@pytest.mark.parametrize("env,use_ht", [({"FASTKMER_DEBUG_LARGE_BUCKETS": "1"}, False),
-                                        ({"FASTKMER_DEBUG_MID_PARTS": "1"}, False),
-                                        ({"FASTKMER_DEBUG_SPLIT_RETRY": "1"}, False),
-                                        ({"FASTKMER_DEBUG_CELL_TARGET": "8192"}, False),
-                                        ({"FASTKMER_DEBUG_CELL_TARGET": "8192", "FASTKMER_DEBUG_FOLD_WMAX": "2"}, False),
-                                        ({}, True)])
+# What a parameter set reaches, by stats() and the census (debug_tier_stats): with the default cells
+# (2^4 per bin of this input) the buckets above the wave tier are 45 of one minimizer cluster each,
+# which the split hands whole to the big table -- FASTKMER_DEBUG_MID_PARTS and _SPLIT_RETRY alone meet
+# no mid-tier bucket and no split one.  Cells of 8192 keys give the mid tier, the split, the big table
+# and the streaming path their buckets, so those hooks are also set together with them.
+BIG_CELLS = {"FASTKMER_DEBUG_CELL_TARGET": "8192"}
+REACHES = {
+    "streaming_all": lambda st, ts: st["oversize_buckets"] >= 1 and ts["nlarge"] == st["oversize_buckets"],
+    "big_table": lambda st, ts: st["big_buckets"] >= 1 and ts["nfbG"] > ts["nlarge"] >= 1,
+    "mid_whole": lambda st, ts: st["block_buckets"] >= 1 and ts["mid_mode"] == "whole",
+    "mid_ranges": lambda st, ts: st["block_buckets"] >= 1 and ts["mid_mode"] == "ranges",
+    "mid_1024": lambda st, ts: st["block_buckets"] >= 1 and ts["mid_mode"] is None,
+    "split": lambda st, ts: st["split_buckets"] >= 1 and st["sub_buckets"] >= 2 * st["split_buckets"],
+}
+
+
+# (env, use_ht, what the set reaches); the first six are the sets the test began with
+TIER_SETS = [
+    ({"FASTKMER_DEBUG_LARGE_BUCKETS": "1"}, False, ["streaming_all"]),
+    ({"FASTKMER_DEBUG_MID_PARTS": "1"}, False, ["big_table"]),
+    ({"FASTKMER_DEBUG_SPLIT_RETRY": "1"}, False, ["big_table"]),
+    (BIG_CELLS, False, ["mid_whole", "split", "big_table"]),
+    ({**BIG_CELLS, "FASTKMER_DEBUG_FOLD_WMAX": "2"}, False, ["mid_whole", "split", "big_table"]),
+    ({}, True, ["big_table"]),
+    ({**BIG_CELLS, "FASTKMER_DEBUG_MID_PARTS": "1"}, False, ["mid_ranges", "split", "big_table"]),
+    ({**BIG_CELLS, "FASTKMER_DEBUG_MID_PARTS": "0"}, False, ["mid_1024", "split", "big_table"]),
+    ({**BIG_CELLS, "FASTKMER_DEBUG_SPLIT_RETRY": "1"}, False, ["mid_whole", "split", "big_table"]),
+    ({**BIG_CELLS, "FASTKMER_DEBUG_MID_PARTS": "1"}, True, ["mid_ranges", "split", "big_table"]),
+]
+
+
+@pytest.mark.parametrize("env,use_ht", [(e, h) for e, h, _ in TIER_SETS])
 def test_every_tier_sees_weights(forced, monkeypatch, env, use_ht):
+    reaches = next(r for e, h, r in TIER_SETS if e == env and h == use_ht)
     for name, v in env.items():
         monkeypatch.setenv(name, v)
     kc = count_pinned(skewed(), 28, 10, use_ht=use_ht)
@@ -152,6 +179,9 @@ def test_every_tier_sees_weights(forced, monkeypatch, env, use_ht):
         assert kc.stats()["pieces_counted"] == 0 and kc.fold_stats()["pieces_folded"] == 0
     else:
         assert_folded(kc)
+    st, ts = kc.stats(), kc.debug_tier_stats()
+    for what in reaches:
+        assert REACHES[what](st, ts), (what, st, ts)
     assert_same_as_oracle(kc, ref_of("skewed"), ordered=not use_ht)
 
 
