@@ -63,6 +63,13 @@ class fk_stats(ctypes.Structure):
                                        ("sub_buckets", ctypes.c_uint64)]
 
 
+class fk_db_info(ctypes.Structure):
+    """Mirror of fk_db_info (include/fastkmer.h): the header of a database file."""
+    _fields_ = [(n, ctypes.c_int32) for n in
+                ("k", "m", "bins", "key_words", "n_ranks", "rank", "version", "stored_bins")] + \
+               [(n, ctypes.c_uint64) for n in ("distinct", "kmers", "checksum", "file_bytes")]
+
+
 class fk_read_stat(ctypes.Structure):
     """Mirror of fk_read_stat (include/fastkmer.h): one read's statistics, 32 bytes."""
     _fields_ = [(n, ctypes.c_uint32) for n in ("windows", "hits", "min", "median", "max", "reserved")] + \
@@ -179,6 +186,14 @@ def lib():
                                                ctypes.c_uint32, P]),
         "fk_get_bin_joined": (ctypes.c_int, [P, P, I32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                              ctypes.c_uint32, P, P, P, SZ, ctypes.POINTER(SZ)]),
+        "fk_export": (ctypes.c_int, [P, P, P, SZ, ctypes.POINTER(SZ)]),
+        "fk_export_device": (ctypes.c_int, [P, P, P, SZ, ctypes.POINTER(SZ)]),
+        "fk_import": (ctypes.c_int, [P, P, P, P]),
+        "fk_import_device": (ctypes.c_int, [P, P, P, P]),
+        "fk_db_info_read": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(fk_db_info)]),
+        "fk_save": (ctypes.c_int, [P, ctypes.c_char_p]),
+        "fk_load": (ctypes.c_int, [P, ctypes.c_char_p]),
+        "fk_debug_store_ms": (ctypes.c_int, [P, P]),
         "fk_map_bin_kmers": (ctypes.c_int, [P, P]),
         "fk_lpt_owners": (ctypes.c_int, [P, I32, I32, P]),
         "fk_set_bin_owners": (ctypes.c_int, [P, P, P]),
@@ -321,6 +336,16 @@ def reads_csr(text, input_format: str = "fasta", min_quality: int = 0, quality_o
     _check(L.fk_reads_csr(*args, bases.ctypes.data, bases.size, offsets.ctypes.data, nr.value, ctypes.byref(nr),
                           ctypes.byref(nb)))
     return bases, offsets
+
+
+def db_info(path: str) -> dict:
+    """fk_db_info_read: the validated header of a database file written by KmerCounter.save -- k, m, bins,
+    key_words, n_ranks, rank, version, stored_bins, distinct, kmers, checksum, file_bytes.  Host only.
+    FastKmerError: FK_E_INVALID for bytes that are no header of this version, FK_E_IO for a file that
+    cannot be read or whose size is not the one its header gives."""
+    h = fk_db_info()
+    _check(lib().fk_db_info_read(os.fsencode(path), ctypes.byref(h)))
+    return {n: int(getattr(h, n)) for n, _ in fk_db_info._fields_}
 
 
 def read_stats_scratch_bytes(n_bases: int) -> int:
@@ -840,6 +865,101 @@ class KmerCounter:
                                                     ctypes.c_void_p(d_offsets), n_reads, int(min_count),
                                                     MAX_COUNT if max_count is None else int(max_count),
                                                     ctypes.c_void_p(d_stats)))
+
+    # -- export, import and the database file (fk_export*, fk_import*, fk_save, fk_load); use_ht = False only
+    def export_arrays(self):
+        """The whole result as (keys, counts, bin_sizes): the bins this rank owns in the order of its
+        local bins (ascending bin id under the default placement), each bin get_bin's keys and counts;
+        bin_sizes (all num_bins entries) gives the cut points."""
+        sizes = self.bin_sizes()
+        d = int(sizes.sum())
+        kw = 2 if self.k > 32 else 1
+        keys = np.zeros(max(d, 1) * kw, dtype=np.uint64)
+        counts = np.zeros(max(d, 1), dtype=np.uint32)
+        n = ctypes.c_size_t(0)
+        _check(lib().fk_export(self._h, keys.ctypes.data, counts.ctypes.data, max(d, 1), ctypes.byref(n)))
+        return keys[:n.value * kw], counts[:n.value], sizes
+
+    def export_ptr(self, d_keys: int, d_counts: int, cap: int) -> int:
+        """fk_export_device: the same arrays at device pointers holding cap k-mers, queued on the context's
+        stream (set_stream); returns the result's distinct k-mers."""
+        n = ctypes.c_size_t(0)
+        _check(lib().fk_export_device(self._h, ctypes.c_void_p(d_keys) if d_keys else None,
+                                      ctypes.c_void_p(d_counts) if d_counts else None, int(cap), ctypes.byref(n)))
+        return n.value
+
+    def _bin_sizes_arg(self, bin_sizes) -> np.ndarray:
+        sz = np.ascontiguousarray(bin_sizes, dtype=np.uint64).reshape(-1)
+        if sz.size != self.num_bins:
+            raise ValueError(f"bin_sizes needs {self.num_bins} entries")
+        return sz
+
+    def import_arrays(self, keys, counts, bin_sizes) -> None:
+        """fk_import, the inverse of export_arrays: afterwards the counter is as after finish().
+        FastKmerError (FK_E_INVALID) naming the bin, the index inside it and the reason for the first key
+        that is no canonical k-mer of its bin in ascending order with a count >= 1."""
+        kw = 2 if self.k > 32 else 1
+        sz = self._bin_sizes_arg(bin_sizes)
+        k = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1)
+        c = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+        if k.size != int(sz.sum()) * kw or c.size != int(sz.sum()):
+            raise ValueError("keys and counts hold sum(bin_sizes) k-mers")
+        self._sizes = None
+        _check(lib().fk_import(self._h, k.ctypes.data, c.ctypes.data, sz.ctypes.data))
+
+    def import_ptr(self, d_keys: int, d_counts: int, bin_sizes) -> None:
+        """fk_import_device: keys and counts at device pointers, bin_sizes on the host."""
+        sz = self._bin_sizes_arg(bin_sizes)
+        self._sizes = None
+        _check(lib().fk_import_device(self._h, ctypes.c_void_p(d_keys) if d_keys else None,
+                                      ctypes.c_void_p(d_counts) if d_counts else None, sz.ctypes.data))
+
+    def import_bins(self, bins: dict) -> None:
+        """import_arrays from {bin: (keys, counts)}; bins left out are empty (default placement only)."""
+        kw = 2 if self.k > 32 else 1
+        sz = np.zeros(self.num_bins, dtype=np.uint64)
+        ks, cs = [], []
+        for b in sorted(bins):  # the local bins' order under the default placement
+            k = np.ascontiguousarray(bins[b][0], dtype=np.uint64).reshape(-1)
+            c = np.ascontiguousarray(bins[b][1], dtype=np.uint32).reshape(-1)
+            if not 0 <= b < self.num_bins or k.size != c.size * kw:
+                raise ValueError(f"bin {b}: outside [0, {self.num_bins}) or keys and counts of different lengths")
+            sz[b] = c.size
+            ks.append(k)
+            cs.append(c)
+        self.import_arrays(np.concatenate(ks) if ks else np.zeros(0, np.uint64),
+                           np.concatenate(cs) if cs else np.zeros(0, np.uint32), sz)
+
+    def save(self, path: str) -> None:
+        """fk_save: the result as a database file (format: INTEGRATION.md "Saving and loading results")."""
+        _check(lib().fk_save(self._h, os.fsencode(path)))
+
+    def load_into(self, path: str) -> None:
+        """fk_load into this counter: its k, m, bin count and key width must be the file's, and it must
+        own every bin the file stores."""
+        self._sizes = None
+        _check(lib().fk_load(self._h, os.fsencode(path)))
+
+    @classmethod
+    def load(cls, path: str, x: int = 3, device: int = -1, n_ranks: int | None = None, rank: int | None = None):
+        """A counter created from the file's header (k, m, bins) and loaded.  The file of one rank of a
+        multi-rank job loads into a one-rank counter unless n_ranks / rank name the saver's."""
+        h = db_info(path)
+        kc = cls(h["k"], h["m"], x, h["bins"], n_ranks=1 if n_ranks is None else n_ranks,
+                 rank=0 if rank is None else rank, device=device)
+        try:
+            kc.load_into(path)
+        except Exception:
+            kc.close()
+            raise
+        return kc
+
+    def store_ms(self) -> dict:
+        """Measurement hook (fk_debug_store_ms): the last save / load / import of this counter in ms."""
+        out = (ctypes.c_double * 8)()
+        _check(lib().fk_debug_store_ms(self._h, out))
+        return {"wall": out[0], "device_copy": out[1], "host_copy_or_read": out[2], "write": out[3],
+                "verify": out[4], "cells": out[5], "buckets": out[6]}
 
     def bin_dict(self, b: int, min_count: int = 1, max_count: int | None = None) -> dict:
         keys, counts = self.get_bin(b, min_count, max_count)

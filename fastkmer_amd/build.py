@@ -20,7 +20,7 @@ CLI = os.path.join(PKG, "bin", "fastkmer-cli")
 ARCH = os.environ.get("FASTKMER_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-LIB_SOURCES = ["fk_kernels.hip", "fk_api.cpp", "fk_views.cpp", "fk_comm.cpp", "fk_split.cpp"]
+LIB_SOURCES = ["fk_kernels.hip", "fk_api.cpp", "fk_views.cpp", "fk_store.cpp", "fk_comm.cpp", "fk_split.cpp"]
 DEPS = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".inc", ".h")) or f in LIB_SOURCES)
 
 

@@ -461,7 +461,7 @@ FK_EXPORT int fk_set_stream(fk_ctx *c, void *s) {
 FK_EXPORT size_t fk_record_bytes(const fk_ctx *c) { return c ? (size_t)c->W * 8 : 0; }
 FK_EXPORT int32_t fk_num_bins(const fk_ctx *c) { return c ? c->Bc : 0; }
 
-static void reset_results(fk_ctx *c) {
+void reset_results(fk_ctx *c) {
     c->mapped = false;
     c->have_result = false;
     c->gapped = c->dense_ready = false;
@@ -1464,7 +1464,7 @@ static bool staged_ok(const fk_ctx *c) {
     return c->cfg.k <= 63 && !c->force_large;
 }
 
-static SortedPlan sorted_plan(const fk_ctx *c, uint64_t max_bin_kmers, int force_F = 0) {
+SortedPlan sorted_plan(const fk_ctx *c, uint64_t max_bin_kmers, int force_F) {
     SortedPlan pl;
     const int k = c->cfg.k;
     const uint32_t cap = 2048;  // keys per LDS bucket (k_bucket_count64 / 128-bit k_bucket_sort)

@@ -29,6 +29,10 @@
 //       configuration, input format and quality settings and the two results are compared:
 //       <outputDir>/compare.tsv, "<count in the input>\t<count in file>\t<distinct k-mers>\n" for the nonzero
 //       entries of the joint count matrix (fk_compare), row-major; needs useHT = 0, else a usage error
+//       a <file> that begins with the database magic "FKMERDB\0" (FASTKMER_CLI_SAVE, fk_save) is loaded
+//       (fk_load) instead of counted
+//   FASTKMER_CLI_SAVE=<file>  after the count, the result is saved as a database file (fk_save); needs
+//       useHT = 0, else a usage error
 //   FASTKMER_CLI_COMPARE_N=<n>  rows = cols = n of that matrix, 2 .. 4096 (default 256): the last row and
 //       column collect the counts >= n - 1
 #include <stdio.h>
@@ -151,6 +155,12 @@ int main(int argc, char **argv) {
         fprintf(stderr, "FASTKMER_CLI_COMPARE needs the sorted count (useHT = 0): a useHT = 1 result cannot be looked up\n");
         return usage(argv[0]);
     }
+    const char *save_path = getenv("FASTKMER_CLI_SAVE");
+    if (save_path && !save_path[0]) save_path = nullptr;
+    if (save_path && cfg.use_ht) {
+        fprintf(stderr, "FASTKMER_CLI_SAVE needs the sorted count (useHT = 0): a useHT = 1 result cannot be looked up\n");
+        return usage(argv[0]);
+    }
     char outdir[4096];
     fk_output_dir(&cfg, output, prefix, outdir, sizeof(outdir));
     // TestConfiguration.toString (test/package.scala:37-39)
@@ -265,6 +275,14 @@ int main(int argc, char **argv) {
         }
         printf("Spectrum written to %s\n", path.c_str());
     }
+    if (save_path) {
+        if (fk_save(ctx, save_path) != FK_OK) {
+            fprintf(stderr, "FASTKMER_CLI_SAVE: %s\n", fk_last_error());
+            fk_destroy(ctx);
+            return 1;
+        }
+        printf("Database written to %s\n", save_path);
+    }
     if (reads_path) {
         std::vector<uint8_t> text;
         FILE *in = fopen(reads_path, "rb");
@@ -332,19 +350,25 @@ int main(int argc, char **argv) {
             fk_destroy(ctx);
             return 1;
         }
-        // the second sample is counted as the job's input was (auto picked the job's format above)
+        // the second sample is a saved database, or is counted as the job's input was (auto picked the job's
+        // format above)
+        const bool is_db = text.size() >= 8 && !memcmp(text.data(), "FKMERDB\0", 8);
         fk_ctx *other = nullptr;
         int crc = fk_create(&cfg, &other);
-        if (crc == FK_OK && format != FK_FORMAT_FASTA)
+        if (is_db) {
+            text.clear();
+            if (crc == FK_OK) crc = fk_load(other, compare_path);
+        }
+        if (crc == FK_OK && !is_db && format != FK_FORMAT_FASTA)
             crc = fk_set_input_format(other, format, (int32_t)min_qual, (int32_t)qual_off);
-        if (crc == FK_OK) crc = fk_ingest_reserve(other, text.size());
-        for (size_t off = 0; crc == FK_OK && (off < text.size() || off == 0);) {
+        if (crc == FK_OK && !is_db) crc = fk_ingest_reserve(other, text.size());
+        for (size_t off = 0; crc == FK_OK && !is_db && (off < text.size() || off == 0);) {
             const size_t len = std::min(window, text.size() - off);
             crc = fk_ingest(other, text.empty() ? nullptr : text.data() + off, len, off + len >= text.size() ? 1 : 0);
             off += len;
             if (text.empty()) break;
         }
-        if (crc == FK_OK) crc = fk_finish(other);
+        if (crc == FK_OK && !is_db) crc = fk_finish(other);
         std::vector<uint64_t> mat((size_t)(cmp_n * cmp_n), 0);
         if (crc == FK_OK) crc = fk_compare(ctx, other, mat.data(), (size_t)cmp_n, (size_t)cmp_n);
         if (crc != FK_OK) {

@@ -1,6 +1,6 @@
 // fk_ctx.h -- private: the context behind the C-ABI's fk_ctx and the host helpers shared by fk_api.cpp (the
-// context, the input and the count) and fk_views.cpp (the calls that only read a finished result).  Both are
-// compiled with the same -D flags (fk_ctx has FK_PROBES members).
+// context, the input and the count), fk_views.cpp (the calls that only read a finished result) and fk_store.cpp
+// (export, import and the database file).  All are compiled with the same -D flags (fk_ctx has FK_PROBES members).
 #pragma once
 
 #include <algorithm>
@@ -16,6 +16,8 @@
 namespace fk {
 int set_err(int code, const char *fmt, ...);  // fk_api.cpp: the calling thread's fk_last_error message; returns code
 int mkdir_p(const std::string &path);         // fk_views.cpp
+// what the lookups, the comparison's kin and the export / import answer on a use_ht = 1 context
+constexpr const char *MSG_NEED_SORTED = "lookups need the sorted count (use_ht = 0): a use_ht = 1 result is in table order";
 
 #define HIP_TRY(expr)                                                                                \
     do {                                                                                             \
@@ -202,6 +204,8 @@ struct fk_ctx {
                                // buckets on the 512-key table always (2), the 1024-key kernel only (0), by size (-1)
     bool split_retry = false;  // FASTKMER_DEBUG_SPLIT_RETRY: every split bucket cut a second time
     bool spectrum_wide = false;  // FASTKMER_DEBUG_SPECTRUM_WIDE: the spectrum kernel of results of >= 2^32 k-mers
+    uint32_t import_bucket = 0;  // FASTKMER_DEBUG_IMPORT_BUCKET=<keys>: an imported result's buckets are cut at this
+                                 // many keys (0: the wave tier's capacity); read by every fk_import* / fk_load
     int x2_l1 = 0;             // FASTKMER_X2_L1: level-1 workgroup size (512, 1024; 0 = by fan-out)
     int fused = 1;             // FASTKMER_FUSED=0: two-kernel map (parse, then signature) for every input
 #ifdef FK_PROBES
@@ -308,6 +312,7 @@ struct fk_ctx {
     uint64_t res_nbuckets = 0;
     int res_F = 0;
     ViewBufs vw;
+    double store_ms[8] = {};              // the last fk_save / fk_load / fk_import* (fk_debug_store_ms)
     // "this context's result is complete", recorded on its stream when another context's comparison looks k-mers up in it
     hipEvent_t cmp_ev = nullptr;
 
@@ -393,6 +398,11 @@ struct fk_ctx {
         std::vector<XSeg> segs;
     } xch;
 };
+
+// fk_api.cpp, shared with fk_store.cpp: the cells of a count whose largest bin holds max_bin_kmers keys, and
+// "the context holds no result"
+SortedPlan sorted_plan(const fk_ctx *c, uint64_t max_bin_kmers, int force_F = 0);
+void reset_results(fk_ctx *c);
 
 // How bins map to ranks and to a rank's local bins (default placement, or fk_set_bin_owners).
 inline const uint32_t *owner_table(const fk_ctx *c) { return c->custom_owners ? c->d_owner.as<uint32_t>() : nullptr; }

@@ -411,6 +411,42 @@ hipError_t launch_join_compact(int KW, const QueryTables &a, const QueryTables &
                                uint32_t olo, uint32_t ohi, const uint64_t *keep_off, uint64_t *fkeys,
                                uint32_t *fcounts, uint32_t *fother, hipStream_t s);
 
+// ---- a result built from dense sorted keys and counts, and the database checksum (fk_store.inc).
+// The dense arrays are fk_export's: every local bin's distinct keys ascending, the bins back to back at
+// bin_off[0 .. nlb] (device).
+struct StoreTables {
+    const uint32_t *owner, *local;  // size-aware placement: bin -> rank, bin -> local bin (null: bin % G, bin / G)
+    FastMod fm;
+    uint32_t G, rank, nlb;
+    int k, m;
+};
+// why a key is refused (launch_store_verify), in the order they are checked
+enum : uint32_t {
+    STORE_BAD_BITS = 1,    // a bit set above bit 2k - 1
+    STORE_BAD_STRAND = 2,  // greater than its reverse complement
+    STORE_BAD_BIN = 3,     // its signature's bin is not the bin its position says
+    STORE_BAD_DUP = 4,     // equal to its predecessor in the bin
+    STORE_BAD_ORDER = 5,   // below its predecessor in the bin
+    STORE_BAD_COUNT = 6,   // count 0
+};
+// res (4 words, zeroed): res[0] = ~((i << 3) | reason) of the offending key with the smallest dense index
+// i (0: every key passed), res[1] += the checksum's terms over keys and counts (the wrapping sum of
+// store_mix(v ^ (i * 0x9E3779B97F4A7C15)): key words at their index in the key section, counts at 2^63 +
+// their index), res[2] += the counts
+hipError_t launch_store_verify(int KW, const StoreTables &t, const uint64_t *keys, const uint32_t *counts, uint64_t n,
+                               const uint64_t *bin_off, unsigned long long *res, hipStream_t s);
+// res[1] / res[2] alone, over nwords key words and n counts
+hipError_t launch_store_checksum(const uint64_t *words, uint64_t nwords, const uint32_t *counts, uint64_t n,
+                                 unsigned long long *res, hipStream_t s);
+// cell_base[(lb << F) + cell] = the dense index of bin lb's first key in a cell >= cell, (nlb << F) + 1
+// entries (the exclusive scan of cell_total, its last word the keys); res[3] |= 1 for a cell of >= 2^32 keys
+hipError_t launch_store_cells(int KW, const uint64_t *keys, const uint64_t *bin_off, uint32_t nlb, int k, int F,
+                              uint64_t *cell_base, uint64_t *cell_total, unsigned long long *res, hipStream_t s);
+// launch_bucket_finish for buckets cut from cell_base (begin = the dense index), their number read on the
+// device (*nb_dev <= nb_max): n, c1, and dense_off[q] = begin, dense_off[*nb_dev] = *total_keys
+hipError_t launch_store_finish(Bucket *buckets, const uint64_t *nb_dev, uint64_t nb_max, uint32_t nlb, int F,
+                               const uint64_t *total_keys, uint64_t *dense_off, hipStream_t s);
+
 // ---- test hook: the 128-bit wave tier's fingerprints cut to `bits` low bits (0: whole), current device
 hipError_t set_fingerprint_bits(int bits);
 

@@ -350,6 +350,7 @@ hipError_t scan_excl_max_i64(const int64_t *in, int64_t *out, uint64_t n, ScanWo
 #include "fk_spectrum.inc"
 #include "fk_compare.inc"
 #include "fk_reads.inc"
+#include "fk_store.inc"
 
 // Test hook of the failure semantics (fk_debug_comm_hold): one thread spins on a host-mapped flag
 // with s_sleep between its system-scope loads, and leaves by itself after max_ticks of the 100 MHz

@@ -109,8 +109,7 @@ static uint64_t query_chunk() {
 
 // the sorted count's bucket-major arrays as the lookup kernel reads them
 static int query_tables(fk_ctx *c, QueryTables &t) {
-    if (c->cfg.use_ht)
-        return set_err(FK_E_INVALID, "lookups need the sorted count (use_ht = 0): a use_ht = 1 result is in table order");
+    if (c->cfg.use_ht) return set_err(FK_E_INVALID, "%s", MSG_NEED_SORTED);
     if (!c->have_result || !c->gapped) return set_err(FK_E_STATE, "no result: call fk_finish or fk_reduce first");
     t.flag_scan = c->res_fs;
     t.buckets = c->buckets.as<Bucket>();

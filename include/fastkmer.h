@@ -557,6 +557,82 @@ int fk_read_stats(fk_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, si
                   uint32_t min_count, uint32_t max_count, fk_read_stat *stats);
 size_t fk_read_stats_scratch_bytes(size_t n_bases);
 
+/* ---- export, import and the database file (no reference counterpart) ----
+ * A counted result taken out of its context and put back: as arrays (a caller
+ * holding (k-mer, count) pairs gets fk_query, fk_read_stats and fk_compare), or
+ * as a binary file that outlives the process (jellyfish .jf, KMC .kmc_pre /
+ * .kmc_suf).  Sorted count only: use_ht == 1 gives FK_E_INVALID.
+ * The dense layout: the bins this rank owns in the order of its local bins
+ * (ascending bin id under the default placement), each bin holding fk_get_bin's
+ * keys (one word for k <= 32, (hi, lo) above) and counts; fk_bin_sizes gives the
+ * cut points.
+ *   fk_export: the whole result in that layout.  *n = the distinct k-mers, always
+ *     set; FK_E_RANGE when cap < *n.  Reads the result only.
+ *   fk_export_device: device pointers; only queues on the context's stream.
+ *   fk_import: the inverse.  bin_sizes (host, all b entries) = the keys of every
+ *     bin; a non-zero size for a bin this context does not own is FK_E_INVALID.
+ *     Every key must be a k-mer (no bit above 2k - 1), canonical (not greater
+ *     than its reverse complement), in the bin its position says, strictly above
+ *     its predecessor in the bin, and have a count >= 1: else FK_E_INVALID, the
+ *     message naming the bin, the index inside the bin and the reason, for the
+ *     offending key with the smallest index.  A cell of 2^32 keys or more is
+ *     FK_E_RANGE.  FK_E_STATE inside a job (between its first fk_ingest and
+ *     fk_finish).  The arrays are copied: they are free once the call returns.
+ *     On success the context is as fk_finish leaves it for every result call and
+ *     a following job works; fk_get_stats reports distinct, kmers (the sum of the
+ *     counts), buckets and fine_bits, every time and map figure 0.  On failure
+ *     the context holds no result (result calls: FK_E_STATE).  As with a new job,
+ *     no fk_compare_device of another context may be outstanding on this one.
+ *   fk_import_device: d_keys / d_counts on the context's device, bin_sizes on the
+ *     host; the work is queued on the context's stream and the call waits for it
+ *     once, to read the verdict.
+ * The file (version 1; little-endian, no timestamps: saving the same result
+ * twice gives identical bytes):
+ *   offset 0   8 bytes   magic "FKMERDB\0"
+ *          8   u32       version = 1
+ *         12   u32       header bytes (a multiple of 8): 72 + 16 * stored_bins
+ *         16   6 x i32   k, m, bins (the clamped b), key_words (1 or 2), n_ranks,
+ *                        rank of the saver
+ *         40   u32       stored_bins;  44  u32  0
+ *         48   3 x u64   distinct, kmers (the sum of the counts), checksum
+ *         72   stored_bins x {u32 bin, u32 0, u64 distinct}: the non-empty bins
+ *                        only, ascending
+ *   header bytes         distinct x key_words x 8: the keys, bin after bin
+ *   after the keys       distinct x 4: the counts
+ * checksum = the wrapping 64-bit sum of mix(v ^ (i * 0x9E3779B97F4A7C15)) over the
+ * key words v (i = the word's index in the key section) and the counts (i = 2^63
+ * + the count's index), mix = splitmix64's finaliser.  x, sequence_type and the
+ * requested B are not stored: the bin function needs only k, m and b.
+ *   fk_db_info_read: host only, and the only parser of the file's bytes.
+ *     Validates the magic and the version, header bytes against stored_bins, the
+ *     bins ascending, unique and below `bins`, their sizes non-zero and summing
+ *     to distinct, key_words against k (FK_E_INVALID), and the file's size
+ *     against the header (FK_E_IO: "truncated" or "trailing bytes").
+ *   fk_save: export, checksum on the device, copy out through two pinned windows
+ *     while the previous one is written; <path>.tmp, then rename.  FK_E_IO with
+ *     errno's text on a file error.  An empty result saves a header with no bins.
+ *   fk_load: the header checked against the context -- k, m, bins, key_words
+ *     (FK_E_INVALID naming the field) and every stored bin owned by it: a file
+ *     saved by rank r of n loads into a context of the same rank and placement,
+ *     and into a one-rank context -- then the sections streamed in and fk_import's
+ *     checks; a checksum or kmers mismatch is FK_E_INVALID. */
+typedef struct fk_db_info {
+    int32_t k, m, bins, key_words, n_ranks, rank, version, stored_bins;
+    uint64_t distinct, kmers, checksum, file_bytes;
+} fk_db_info;
+int fk_export(fk_ctx *ctx, uint64_t *keys, uint32_t *counts, size_t cap, size_t *n);
+int fk_export_device(fk_ctx *ctx, void *d_keys, void *d_counts, size_t cap, size_t *n);
+int fk_import(fk_ctx *ctx, const uint64_t *keys, const uint32_t *counts, const uint64_t *bin_sizes);
+int fk_import_device(fk_ctx *ctx, const void *d_keys, const void *d_counts, const uint64_t *bin_sizes);
+int fk_db_info_read(const char *path, fk_db_info *out);
+int fk_save(fk_ctx *ctx, const char *path);
+int fk_load(fk_ctx *ctx, const char *path);
+/* Measurement hook: the last fk_save / fk_load / fk_import* of the context in ms -- out[0] wall,
+ * out[1] export + checksum (save) or H2D of the arrays (device events), out[2] the copy out (save: the
+ * host's waits for its windows) or the file reads (load), out[3] the file writes, out[4..7) the
+ * import's verify, cell offsets and bucket tables (device events), out[7] = 0. */
+int fk_debug_store_ms(const fk_ctx *ctx, double out[8]);
+
 /* ---- test hook (no reference counterpart) ----
  * One bucket through the wave-tier count kernel on `device`: the n keys
  * (k <= 32: one word each, n <= 512; 33 <= k <= 63: (hi, lo) pairs, n <= 256)
