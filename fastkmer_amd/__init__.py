@@ -223,6 +223,7 @@ def lib():
         "fk_debug_count_pieces": (ctypes.c_int, [P, I32, I32, P, P, I32, ctypes.c_uint32]),
         "fk_debug_tier_stats": (ctypes.c_int, [P, P]),
         "fk_debug_staged_piece": (ctypes.c_int, [P, I32, P, P]),
+        "fk_debug_live_resources": (ctypes.c_int, [P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -1075,6 +1076,14 @@ def debug_wave_count(keys: np.ndarray, k: int, F: int, c0: int, c1: int, slots: 
     _check(fn(device, k, F, c0, c1, slots, keys.ctypes.data, n, ok.ctypes.data, oc.ctypes.data, ctypes.byref(nout)))
     u = nout.value
     return (ok[:u] if kw == 1 else ok[:2 * u].reshape(-1, 2)), oc[:u]
+
+
+def live_resources() -> tuple[int, int, int, int]:
+    """Test hook (fk_debug_live_resources): the device allocations, pinned host allocations, events and
+    streams the library's contexts and calls hold in this process right now."""
+    out = (ctypes.c_uint64 * 4)()
+    _check(lib().fk_debug_live_resources(out))
+    return tuple(int(v) for v in out)
 
 
 def comm_unique_id() -> bytes:

@@ -15,6 +15,7 @@
 
 #include <unordered_map>
 #include <chrono>
+#include <memory>
 #include <cstdlib>
 #include <cstring>
 #include <thread>
@@ -232,26 +233,8 @@ FK_EXPORT int fk_synth_fasta_host(uint8_t *out, uint64_t first_read, uint64_t n_
 // context
 // ---------------------------------------------------------------------------
 
-FK_EXPORT int fk_create(const fk_config *cfg, fk_ctx **out) {
-    if (!out) return set_err(FK_E_INVALID, "null output pointer");
-    *out = nullptr;
-    FK_TRY(fk_config_validate(cfg));
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        return set_err(FK_E_DEVICE, "no HIP device available (%s): the k-mer counter runs on MI355X only",
-                       hipGetErrorString(e));
-    }
-    fk_ctx *c = new fk_ctx();
-    c->cfg = *cfg;
-    c->Bc = clamp_bins(cfg->m, cfg->B);
-    c->G = (uint32_t)cfg->n_ranks;
-    c->nlb = (uint32_t)((c->Bc - cfg->rank + (int)c->G - 1) / (int)c->G);
-    if (cfg->rank >= c->Bc) c->nlb = 0;
-    c->W = cfg->k <= 32 ? 2 : 3;
-    c->KW = cfg->k <= 32 ? 1 : 2;
-    c->fm = make_fastmod((uint32_t)c->Bc);
+// What the environment sets in a new context.
+static void read_env(fk_ctx *c) {
     // The product library reads thirteen variables: three sizes of the streamed input, the fold's gate
     // (FASTKMER_FOLD), the lookups' staging chunk (FASTKMER_QUERY_CHUNK, read by every fk_query /
     // fk_query_sequence call) and eight test
@@ -294,9 +277,34 @@ FK_EXPORT int fk_create(const fk_config *cfg, fk_ctx **out) {
     if (const char *v = env("FASTKMER_FUSED_PROBE")) c->fused_probe = atoi(v);
     if (const char *v = env("FASTKMER_SPLIT_MAP")) c->split_map = atoi(v);
 #endif
+}
+
+FK_EXPORT int fk_create(const fk_config *cfg, fk_ctx **out) {
+    if (!out) return set_err(FK_E_INVALID, "null output pointer");
+    *out = nullptr;
+    FK_TRY(fk_config_validate(cfg));
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev <= 0) {
+        (void)hipGetLastError();
+        return set_err(FK_E_DEVICE, "no HIP device available (%s): the k-mer counter runs on MI355X only",
+                       hipGetErrorString(e));
+    }
+    // any failure below leaves through this owner: fk_destroy takes a context however far it got
+    std::unique_ptr<fk_ctx, void (*)(fk_ctx *)> ctx(new fk_ctx(), fk_destroy);
+    fk_ctx *c = ctx.get();
+    c->cfg = *cfg;
+    c->Bc = clamp_bins(cfg->m, cfg->B);
+    c->G = (uint32_t)cfg->n_ranks;
+    c->nlb = (uint32_t)((c->Bc - cfg->rank + (int)c->G - 1) / (int)c->G);
+    if (cfg->rank >= c->Bc) c->nlb = 0;
+    c->W = cfg->k <= 32 ? 2 : 3;
+    c->KW = cfg->k <= 32 ? 1 : 2;
+    c->fm = make_fastmod((uint32_t)c->Bc);
+    read_env(c);
     if (cfg->device >= 0) {
         if (cfg->device >= ndev) {
-            delete c;
+            c->device = -1;  // none to select on the way out
             return set_err(FK_E_DEVICE, "device %d out of range (%d devices)", cfg->device, ndev);
         }
         c->device = cfg->device;
@@ -308,153 +316,53 @@ FK_EXPORT int fk_create(const fk_config *cfg, fk_ctx **out) {
         int cur = -1;
         if (hipGetDevice(&cur) != hipSuccess || cur != c->device) {
             (void)hipGetLastError();
-            delete c;
             return set_err(FK_E_DEVICE, "cannot select device %d", c->device);
         }
     }
-    e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) {
-        delete c;
-        return set_err(FK_E_DEVICE, "hipStreamCreate: %s", hipGetErrorString(e));
-    }
-    c->own_stream = true;
-    e = hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->seg_ev, hipEventDisableTiming);
-    // staged pieces are partitioned and expanded on their own stream (one rank: so that the map of
-    // later segments never queues behind a piece's expansion; the exchange: the received segments)
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->xstage, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->xstage_ev, hipEventDisableTiming);
-    // the heavy tiers' stream at the device's highest priority: their kernels are few
-    // and long chains (split, in-order sub-buckets, fallbacks with large workgroups), and at normal
-    // priority they waited for LDS behind the wave tier's millions of one-wave workgroups and ran
-    // alone after it (the configs[2] load's split fallbacks: 13.8 ms of a kernel of ~40 workgroups)
-    if (e == hipSuccess) {
-        int least = 0, greatest = 0;
-        if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess)
-            e = hipStreamCreateWithPriority(&c->tier_side, hipStreamNonBlocking, greatest);
-        else
-            e = hipStreamCreateWithFlags(&c->tier_side, hipStreamNonBlocking);
-    }
-    for (int i = 0; i < 4 && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&c->side_ev[i], hipEventDisableTiming);
-    for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreate(&c->h2d_ev[i]);
-    if (e != hipSuccess) {
-        fk_destroy(c);
-        return set_err(FK_E_DEVICE, "copy stream / events: %s", hipGetErrorString(e));
-    }
-    for (auto &ev : c->ev) {
-        e = hipEventCreate(&ev);
-        if (e != hipSuccess) {
-            fk_destroy(c);
-            return set_err(FK_E_DEVICE, "hipEventCreate: %s", hipGetErrorString(e));
-        }
-    }
-    e = hipEventCreateWithFlags(&c->tier_ev, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->pin_up_ev, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->cmp_ev, hipEventDisableTiming);
-    if (e != hipSuccess) {
-        fk_destroy(c);
-        return set_err(FK_E_DEVICE, "hipEventCreate: %s", hipGetErrorString(e));
-    }
-    for (auto &ev : c->st_ev) {
-        e = hipEventCreate(&ev);
-        if (e != hipSuccess) {
-            fk_destroy(c);
-            return set_err(FK_E_DEVICE, "hipEventCreate: %s", hipGetErrorString(e));
-        }
-    }
-    *out = c;
+    // the streams and events (roles: DESIGN.md, "The context: what lives how long"); an event is timed
+    // unless it only orders streams
+    constexpr unsigned ORDER = hipEventDisableTiming;
+    e = c->stream.create();
+    if (e != hipSuccess) return set_err(FK_E_DEVICE, "hipStreamCreate: %s", hipGetErrorString(e));
+    int least = 0, greatest = 0;
+    const bool prio = hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess;
+    e = c->copy_stream.create();
+    if (e == hipSuccess) e = c->seg_ev.create(ORDER);
+    if (e == hipSuccess) e = c->xstage.create();
+    if (e == hipSuccess) e = c->xstage_ev.create(ORDER);
+    if (e == hipSuccess) e = c->tier_side.create(prio ? &greatest : nullptr);
+    for (int i = 0; i < 4 && e == hipSuccess; ++i) e = c->side_ev[i].create(ORDER);
+    for (int i = 0; i < 2 && e == hipSuccess; ++i) e = c->h2d_ev[i].create();
+    if (e != hipSuccess) return set_err(FK_E_DEVICE, "copy stream / events: %s", hipGetErrorString(e));
+    for (int i = 0; i < 12 && e == hipSuccess; ++i) e = c->ev[i].create();
+    for (Event *ev : {&c->tier_ev, &c->pin_up_ev, &c->cmp_ev})
+        if (e == hipSuccess) e = ev->create(ORDER);
+    for (int i = 0; i < 4 * STAGE_MAXP && e == hipSuccess; ++i) e = c->st_ev[i].create();
+    if (e != hipSuccess) return set_err(FK_E_DEVICE, "hipEventCreate: %s", hipGetErrorString(e));
+    *out = ctx.release();
     return FK_OK;
 }
 
+// Every member that holds a GPU handle frees it when the context is deleted (fk_ctx.h); what is left to do
+// here is to let the work that may still use them end.
 FK_EXPORT void fk_destroy(fk_ctx *c) {
     if (!c) return;
     DeviceGuard dg_(c->device);
-    if (c->hold_flag) __atomic_store_n(c->hold_flag, 1u, __ATOMIC_RELEASE);  // a test's held streams drain
-    if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    // staged expansions (an ingest without fk_finish) read the buffers released below
-    if (c->xstage) (void)hipStreamSynchronize(c->xstage);
-    // and the heavy tiers of a count that failed half way
-    if (c->tier_side) (void)hipStreamSynchronize(c->tier_side);
-    DevBuf *bufs[] = {&c->fasta_own, &c->tile_last_nl, &c->tile_off,
-                      &c->npos_dev, &c->codes, &c->valid, &c->records, &c->counters, &c->sig_status, &c->sig_kmers, &c->tcnt, &c->rec_hdr, &c->rec_pos, &c->rec_code, &c->tstat, &c->map_vslots,
-                      &c->precs, &c->chunks, &c->bin_chunk_begin, &c->hpieces, &c->hpiece_first, &c->hpiece_tot, &c->chunk_nk, &c->grp_table,
-                      &c->chunk_base, &c->lp, &c->scratch,
-                      &c->cell_total, &c->cell_base, &c->flags, &c->flag_scan, &c->buckets, &c->keys,
-                      &c->out_keys, &c->out_counts, &c->bucket_unique, &c->dense_off, &c->dense_keys,
-                      &c->dense_counts, &c->bin_off, &c->misc, &c->tier_list, &c->mid, &c->sc_total,
-                      &c->sp_base, &c->sp_keys, &c->sp_subs, &c->sp_par, &c->sp_fb, &c->mid_fb};
-    for (DevBuf *b : bufs) release(*b);
-    c->vw.release_all();
-    release(c->fq_ws);
-    release(c->fq_info);
-    for (auto &e : c->fq_evs)
-        if (e) (void)hipEventDestroy(e);
-    c->fq_pin.release();
-    for (int i = 0; i < 2; ++i) {
-        if (c->pinned[i]) (void)hipHostFree(c->pinned[i]);
-        if (c->pin_ev[i]) (void)hipEventDestroy(c->pin_ev[i]);
-    }
-    if (c->comm_stream) (void)hipStreamSynchronize(c->comm_stream);
+    if (c->hold_flag.p) __atomic_store_n(c->hold_flag.as<uint32_t>(), 1u, __ATOMIC_RELEASE);  // a test's held streams drain
+    // the copy, the map and count, staged expansions of an ingest without fk_finish, the heavy tiers of a
+    // count that failed half way, the exchange
+    for (hipStream_t s : {(hipStream_t)c->copy_stream, (hipStream_t)c->stream, (hipStream_t)c->xstage,
+                          (hipStream_t)c->tier_side, (hipStream_t)c->comm_stream})
+        if (s) (void)hipStreamSynchronize(s);
     delete c->comm;
-    c->comm = nullptr;
-    c->pin_up.release();
-    c->pin_down.release();
-    c->pin_tier.release();
-    c->fold_pin.release();
-    c->file_pin[0].release();
-    c->file_pin[1].release();
-    if (c->tier_ev) (void)hipEventDestroy(c->tier_ev);
-    if (c->pin_up_ev) (void)hipEventDestroy(c->pin_up_ev);
-    if (c->cmp_ev) (void)hipEventDestroy(c->cmp_ev);
-    if (c->hold_flag) (void)hipHostFree(c->hold_flag);
-    release(c->xsend);
-    release(c->xrecv);
-    for (auto &e : c->xev)
-        if (e) (void)hipEventDestroy(e);
-    for (auto &e : c->seg_evs)
-        if (e) (void)hipEventDestroy(e);
-    for (auto &e : c->map_evs)
-        if (e) (void)hipEventDestroy(e);
-    if (c->emit_ev) (void)hipEventDestroy(c->emit_ev);
-    if (c->comm_stream) (void)hipStreamDestroy(c->comm_stream);
-    if (c->xstage) (void)hipStreamSynchronize(c->xstage), (void)hipStreamDestroy(c->xstage);
-    if (c->xstage_ev) (void)hipEventDestroy(c->xstage_ev);
-    if (c->ws_x.ptr) (void)hipFree(c->ws_x.ptr);
-    c->dest.release_all();
-    c->part.release_all();
-    c->binhist.release_all();
-    release(c->d_owner);
-    release(c->d_local);
-    if (c->ws.ptr) (void)hipFree(c->ws.ptr);
-    for (auto &ev : c->ev)
-        if (ev) (void)hipEventDestroy(ev);
-    for (auto &ev : c->st_ev)
-        if (ev) (void)hipEventDestroy(ev);
-    for (int p = 0; p < STAGE_MAXP; ++p) release(c->st_keys[p]), release(c->st_cb[p]);
-    release(c->st_total);
-    release(c->fold_cnt), release(c->fold_cb), release(c->fold_io);
-    release(c->piece_starts);
-    if (c->seg_ev) (void)hipEventDestroy(c->seg_ev);
-    for (auto &ev : c->h2d_ev)
-        if (ev) (void)hipEventDestroy(ev);
-    if (c->tier_side) (void)hipStreamSynchronize(c->tier_side), (void)hipStreamDestroy(c->tier_side);
-    for (auto &ev : c->side_ev)
-        if (ev) (void)hipEventDestroy(ev);
-    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-    if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
 
 FK_EXPORT int fk_set_stream(fk_ctx *c, void *s) {
     if (!c) return set_err(FK_E_INVALID, "null ctx");
     DeviceGuard dg_(c->device);
-    if (c->own_stream && c->stream) {
-        (void)hipStreamSynchronize(c->stream);
-        (void)hipStreamDestroy(c->stream);
-    }
-    c->stream = (hipStream_t)s;
-    c->own_stream = false;
+    if (c->stream.own) (void)hipStreamSynchronize(c->stream);
+    c->stream.borrow((hipStream_t)s);  // the caller's: never destroyed here
     return FK_OK;
 }
 
@@ -468,6 +376,32 @@ void reset_results(fk_ctx *c) {
     c->distinct = 0;
     c->h_bin_off.clear();
 }
+
+// A new map or count opens: no result, no records, fresh statistics.
+static void new_result(fk_ctx *c) {
+    reset_results(c);
+    c->stats = fk_stats{};
+    c->nrec = c->nkmers = 0;
+    c->rec_tiled = false;
+}
+
+// A job begins (the one place): its state from scratch, the last result gone, and for a FASTQ input the
+// stage's counters zeroed on the map stream.  The callers then set what is particular to their kind of
+// input.  The format is the job's from here on.
+static int begin_job(fk_ctx *c, bool fastq) {
+    c->job = fk_ctx::Job{};
+    reset_results(c);
+    c->job.job_open = true;
+    c->job.fq_job = fastq;
+    if (!fastq) return FK_OK;
+    FK_TRY(ensure(c->fq_info, 32));
+    if (c->fq_pin.ensure(32)) return set_err(FK_E_NOMEM, "hipHostMalloc(32) failed");
+    HIP_TRY(hipMemsetAsync(c->fq_info.p, 0, 32, c->stream));
+    return FK_OK;
+}
+
+// A job's count is done (or given up): its staged pieces are no more, a later count takes the whole input.
+static void end_pieces(fk_ctx *c) { static_cast<fk_ctx::Pieces &>(c->job) = fk_ctx::Pieces{}; }
 
 static float ev_ms(hipEvent_t a, hipEvent_t b) {
     float ms = 0.f;
@@ -487,8 +421,7 @@ static int grow_keep(DevBuf &b, size_t bytes, size_t keep, hipStream_t s) {
     FK_TRY(ensure(g, std::max<size_t>(bytes, 2 * b.bytes)));
     if (keep && b.p) HIP_TRY(hipMemcpyAsync(g.p, b.p, std::min(keep, b.bytes), hipMemcpyDeviceToDevice, s));
     HIP_TRY(hipStreamSynchronize(s));
-    release(b);
-    b = g;
+    b = std::move(g);
     return FK_OK;
 }
 
@@ -496,7 +429,7 @@ static int grow_keep(DevBuf &b, size_t bytes, size_t keep, hipStream_t s) {
 
 FK_EXPORT int fk_set_input_format(fk_ctx *c, int32_t format, int32_t min_quality, int32_t quality_offset) {
     if (!c) return set_err(FK_E_INVALID, "null ctx");
-    if (c->job_open) return set_err(FK_E_STATE, "fk_set_input_format inside a job (after its first fk_ingest)");
+    if (c->job.job_open) return set_err(FK_E_STATE, "fk_set_input_format inside a job (after its first fk_ingest)");
     if (format != FK_FORMAT_FASTA && format != FK_FORMAT_FASTQ) return set_err(FK_E_INVALID, "unknown input format %d", format);
     if (quality_offset != 33 && quality_offset != 64)
         return set_err(FK_E_INVALID, "quality_offset must be 33 or 64, got %d", quality_offset);
@@ -526,33 +459,18 @@ FK_EXPORT int fk_fastq_info(fk_ctx *c, uint64_t out[3]) {
 
 FK_EXPORT int fk_debug_fastq_ms(fk_ctx *c, double *ms, uint64_t *launches) {
     if (!c || !ms || !launches) return set_err(FK_E_INVALID, "null argument");
-    if (!c->fq_have_info || c->job_open) return set_err(FK_E_STATE, "fk_debug_fastq_ms before the fk_map / fk_finish of a FASTQ job");
+    if (!c->fq_have_info || c->job.job_open) return set_err(FK_E_STATE, "fk_debug_fastq_ms before the fk_map / fk_finish of a FASTQ job");
     DeviceGuard dg_(c->device);
     double sum = 0.0;
-    for (size_t i = 0; i + 1 < c->fq_nev; i += 2) sum += ev_ms(c->fq_evs[i], c->fq_evs[i + 1]);
+    for (size_t i = 0; i + 1 < c->job.fq_nev; i += 2) sum += ev_ms(c->fq_evs[i], c->fq_evs[i + 1]);
     *ms = sum;
-    *launches = c->fq_nev / 2;
+    *launches = c->job.fq_nev / 2;
     return FK_OK;
 }
 
 FK_EXPORT int fk_fastq_frontier(const uint8_t *buf, size_t n, size_t *off) {
     if ((!buf && n) || !off) return set_err(FK_E_INVALID, "null argument");
     *off = (size_t)fastq_frontier_scan([buf](uint64_t p) { return buf[p]; }, 0, n);
-    return FK_OK;
-}
-
-// A job's first ingest: the format is the job's from here on.
-static int fq_begin_job(fk_ctx *c, bool fastq) {
-    c->job_open = true;
-    c->fq_job = fastq;
-    c->fq_done = 0;
-    c->fq_tail.clear();
-    c->fq_launched = false;
-    c->fq_nev = 0;
-    if (!fastq) return FK_OK;
-    FK_TRY(ensure(c->fq_info, 32));
-    if (c->fq_pin.ensure(32)) return set_err(FK_E_NOMEM, "hipHostMalloc(32) failed");
-    HIP_TRY(hipMemsetAsync(c->fq_info.p, 0, 32, c->stream));
     return FK_OK;
 }
 
@@ -564,17 +482,13 @@ static int fq_normalise(fk_ctx *c, const uint8_t *src, uint64_t a, uint64_t b, b
         return set_err(FK_E_INVALID, "FASTQ: %llu bytes in one normalise range (a record, or a device input, of 4 GiB or more)",
                        (unsigned long long)(b - a));
     FK_TRY(ensure(c->fq_ws, fastq_ws_bytes(b - a)));
-    while (c->fq_evs.size() < c->fq_nev + 2) {
-        hipEvent_t e = nullptr;
-        HIP_TRY(hipEventCreate(&e));
-        c->fq_evs.push_back(e);
-    }
-    HIP_TRY(hipEventRecord(c->fq_evs[c->fq_nev], c->stream));
+    HIP_TRY(ensure_events(c->fq_evs, c->job.fq_nev + 2));
+    HIP_TRY(hipEventRecord(c->fq_evs[c->job.fq_nev], c->stream));
     HIP_TRY(launch_fastq_normalise(c->fasta_own.as<uint8_t>(), src, a, b, final_ ? 1 : 0, c->fq_min_q, c->fq_q_off,
                                    c->fq_ws.p, c->fq_info.as<unsigned long long>(), c->stream));
-    HIP_TRY(hipEventRecord(c->fq_evs[c->fq_nev + 1], c->stream));
-    c->fq_nev += 2;
-    c->fq_launched = true;
+    HIP_TRY(hipEventRecord(c->fq_evs[c->job.fq_nev + 1], c->stream));
+    c->job.fq_nev += 2;
+    c->job.fq_launched = true;
     return FK_OK;
 }
 
@@ -586,40 +500,40 @@ static int fq_advance(fk_ctx *c, const uint8_t *src, uint64_t have, uint64_t off
     const uint64_t end = have + off;
     uint64_t f = end;
     if (!final_) {
-        const uint64_t tb = have - c->fq_tail.size();  // fq_tail holds [tb, have), tb <= fq_done
-        const std::vector<uint8_t> &tail = c->fq_tail;
+        const uint64_t tb = have - c->job.fq_tail.size();  // fq_tail holds [tb, have), tb <= fq_done
+        const std::vector<uint8_t> &tail = c->job.fq_tail;
         // at most FQ_LOOK bytes back: a record longer than that moves the frontier once the next one is seen
         constexpr uint64_t FQ_LOOK = 16ull << 20;
-        f = fastq_frontier_scan([&](uint64_t p) { return p < have ? tail[p - tb] : src[p - have]; }, c->fq_done, end,
+        f = fastq_frontier_scan([&](uint64_t p) { return p < have ? tail[p - tb] : src[p - have]; }, c->job.fq_done, end,
                                 end > FQ_LOOK ? end - FQ_LOOK : 0);
-        if (f == end) f = c->fq_done;  // no record start in sight (a long read): the frontier stays
+        if (f == end) f = c->job.fq_done;  // no record start in sight (a long read): the frontier stays
     }
-    FK_TRY(fq_normalise(c, nullptr, c->fq_done, f, final_));
-    c->fq_done = f;
+    FK_TRY(fq_normalise(c, nullptr, c->job.fq_done, f, final_));
+    c->job.fq_done = f;
     *limit = f;
     return FK_OK;
 }
 
 // fk_map / fk_signature_counts: what no fk_ingest(..., last = 1) has normalised ends the input.
 static int fq_finish_pending(fk_ctx *c, uint64_t n) {
-    if (!c->fq_job || c->fq_done >= n) return FK_OK;
-    FK_TRY(fq_normalise(c, nullptr, c->fq_done, n, true));
-    c->fq_done = n;
-    c->fq_tail.clear();
+    if (!c->job.fq_job || c->job.fq_done >= n) return FK_OK;
+    FK_TRY(fq_normalise(c, nullptr, c->job.fq_done, n, true));
+    c->job.fq_done = n;
+    c->job.fq_tail.clear();
     return FK_OK;
 }
 
 // Queues the read-back of the job's FASTQ counters behind the normalise launches (the caller's next
 // wait on the map stream covers it) / reads them: FK_E_INVALID for a malformed record.
 static int fq_info_queue(fk_ctx *c) {
-    if (c->fq_job && c->fq_launched)
+    if (c->job.fq_job && c->job.fq_launched)
         HIP_TRY(hipMemcpyAsync(c->fq_pin.p, c->fq_info.p, 32, hipMemcpyDeviceToHost, c->stream));
     return FK_OK;
 }
 static int fq_info_read(fk_ctx *c) {
-    if (!c->fq_job) return FK_OK;
+    if (!c->job.fq_job) return FK_OK;
     const uint64_t *h = c->fq_pin.as<uint64_t>();
-    const bool any = c->fq_launched;
+    const bool any = c->job.fq_launched;
     c->fq_out[0] = any ? h[0] : 0;
     c->fq_out[1] = any ? h[1] : 0;
     c->fq_out[2] = any && h[2] ? ~h[2] : UINT64_MAX;
@@ -665,23 +579,21 @@ static int map_launch(fk_ctx *c, const uint8_t *fa, uint64_t n, int more, uint64
 static int premap_launch(fk_ctx *c, uint64_t landed, bool final_) {
     const uint64_t tile = fm_tile_bytes(FUSED_NT), span = fm_span_bytes(FUSED_NT);
     const uint64_t end = final_ ? (landed + tile - 1) / tile : (landed >= span ? (landed - span) / tile + 1 : 0);
-    if (end <= c->pm_tiles) return FK_OK;
+    if (end <= c->job.pm_tiles) return FK_OK;
     if (c->tcnt.bytes < end * 4 || c->tstat.bytes < end * 8 || c->rec_hdr.bytes < end * map_fused_tcap() * 4 ||
         c->rec_pos.bytes < end * map_fused_tcap() * 2 || c->rec_code.bytes < end * map_fused_cslot() * 4)
         return set_err(FK_E_STATE, "streamed map: %llu tiles exceed the reserved record slots",
                        (unsigned long long)end);
     hipStream_t s = c->stream;
-    if (c->pm_tiles == 0) HIP_TRY(hipEventRecord(c->ev[10], s));
-    FK_TRY(map_launch(c, c->d_fasta, landed, final_ ? 0 : 1, c->pm_tiles, end - c->pm_tiles, s));
-    c->pm_tiles = end;
+    if (c->job.pm_tiles == 0) HIP_TRY(hipEventRecord(c->ev[10], s));
+    FK_TRY(map_launch(c, c->d_fasta, landed, final_ ? 0 : 1, c->job.pm_tiles, end - c->job.pm_tiles, s));
+    c->job.pm_tiles = end;
     if (final_) HIP_TRY(hipEventRecord(c->ev[11], s));
     return FK_OK;
 }
 
 static int xch_maybe_piece(fk_ctx *c);
 static int local_maybe_piece(fk_ctx *c, uint64_t tiles, hipEvent_t mapped);
-static void xch_reset(fk_ctx *c);
-static void pieces_reset(fk_ctx *c);
 
 // Appends host bytes to the device input on the copy stream, in segments.
 // Pinned sources are copied by DMA directly; pageable ones through two
@@ -700,7 +612,7 @@ static int ingest_impl(fk_ctx *c, const uint8_t *fasta, size_t n, int last) {
     if (c->d_fasta && c->d_fasta != c->fasta_own.as<uint8_t>()) {
         // a borrowed device input (fk_ingest_device): host chunks cannot be appended
         // to it, but a host ingest that starts a new job replaces it
-        if (c->dev_open) return set_err(FK_E_STATE, "fk_ingest appending to an fk_ingest_device input");
+        if (c->job.dev_open) return set_err(FK_E_STATE, "fk_ingest appending to an fk_ingest_device input");
         c->d_fasta = nullptr;
     }
     hipStream_t s = c->stream, cs = c->copy_stream;
@@ -709,20 +621,16 @@ static int ingest_impl(fk_ctx *c, const uint8_t *fasta, size_t n, int last) {
         c->n_fasta = 0;
         c->ingest_fresh = false;
         if (c->comm) {
-            if (c->xch.open) return set_err(FK_E_STATE, "fk_ingest: the previous job's exchange is unfinished (fk_finish)");
+            if (c->job.xch.open) return set_err(FK_E_STATE, "fk_ingest: the previous job's exchange is unfinished (fk_finish)");
             FK_TRY(comm_sync(c, c->comm_stream));
-            xch_reset(c);
         }
         FK_TRY(comm_sync(c, c->xstage));
         HIP_TRY(hipStreamSynchronize(c->tier_side));  // (the heavy tiers of a count that failed half way)
         HIP_TRY(hipStreamSynchronize(s));  // a previous job's work may still read the buffers
-        pieces_reset(c);
-        c->pm_active = premap_eligible(c);
-        c->pm_tiles = 0;
-        c->pm_last_seen = false;
-        FK_TRY(fq_begin_job(c, c->in_format == FK_FORMAT_FASTQ));
-    } else if (c->pm_last_seen) {
-        c->pm_active = false;  // appending after the final tiles: fk_map maps the whole input
+        FK_TRY(begin_job(c, c->in_format == FK_FORMAT_FASTQ));
+        c->job.pm_active = premap_eligible(c);
+    } else if (c->job.pm_last_seen) {
+        c->job.pm_active = false;  // appending after the final tiles: fk_map maps the whole input
     }
     const uint64_t have = c->n_fasta, need = have + n;
     if (c->fasta_own.bytes < need) {  // grow, keeping what was ingested (and what the map reads)
@@ -732,9 +640,9 @@ static int ingest_impl(fk_ctx *c, const uint8_t *fasta, size_t n, int last) {
     c->d_fasta = c->fasta_own.as<uint8_t>();
     // FASTQ: every segment is normalised up to the frontier before the map may read it; the map's
     // limit is the frontier where it is `landed` for FASTA
-    const bool fq = c->fq_job;
+    const bool fq = c->job.fq_job;
     if (fq) FK_TRY(ensure(c->fq_ws, fastq_ws_bytes(std::min<uint64_t>(n, 4 * c->ingest_seg) + (1u << 20))));
-    if (c->pm_active) {
+    if (c->job.pm_active) {
         // record slots and per-tile counts of every tile this input can hold (kept on growth)
         const uint64_t tiles = (need + fm_tile_bytes(FUSED_NT) - 1) / fm_tile_bytes(FUSED_NT) + 1;
         if (c->tcnt.bytes < tiles * 4) FK_TRY(grow_keep(c->tcnt, tiles * 4, c->tcnt.bytes, s));
@@ -756,16 +664,16 @@ static int ingest_impl(fk_ctx *c, const uint8_t *fasta, size_t n, int last) {
     (void)hipGetLastError();
     if (!pinned && n)
         for (int i = 0; i < 2; ++i)
-            if (!c->pinned[i]) {
-                HIP_TRY(hipHostMalloc(&c->pinned[i], PIN_CHUNK, hipHostMallocDefault));
-                HIP_TRY(hipEventCreateWithFlags(&c->pin_ev[i], hipEventDisableTiming));
+            if (!c->pinned[i].p) {
+                HIP_TRY(c->pinned[i].alloc(PIN_CHUNK, hipHostMallocDefault));
+                HIP_TRY(c->pin_ev[i].create(hipEventDisableTiming));
                 HIP_TRY(hipEventRecord(c->pin_ev[i], cs));
             }
     // with a communicator, every piece of mapped tiles is exchanged while later ones land
-    const bool pieces = c->comm && c->pm_active;
+    const bool pieces = c->comm && c->job.pm_active;
     // the job's size: this call's when it holds the whole input, else what fk_ingest_reserve announced
     if (pieces && fresh) {
-        c->xch.expect_bytes = last ? n : c->reserve_bytes;
+        c->job.xch.expect_bytes = last ? n : c->reserve_bytes;
         // a job of known size goes out in about XCH_STEPS steps (at most 1 GB, at least XCH_MIN each):
         // every step but the last moves while later bytes are copied in (one 1 GB step for a 1 GB job
         // would leave the whole exchange after the last byte), and the staging cuts (st_cuts) fall on
@@ -774,12 +682,12 @@ static int ingest_impl(fk_ctx *c, const uint8_t *fasta, size_t n, int last) {
         constexpr uint64_t XCH_STEPS = 10;
         constexpr uint64_t XCH_MIN = 64ull << 20;  // a 1 GB job: ten steps (128 MB: seven)
         if (!c->piece_bytes_set)
-            c->piece_bytes = c->xch.expect_bytes
-                                 ? std::min<uint64_t>(1ull << 30, std::max<uint64_t>(XCH_MIN, c->xch.expect_bytes / XCH_STEPS))
+            c->piece_bytes = c->job.xch.expect_bytes
+                                 ? std::min<uint64_t>(1ull << 30, std::max<uint64_t>(XCH_MIN, c->job.xch.expect_bytes / XCH_STEPS))
                                  : 1ull << 30;
     }
     if (fresh) {
-        c->job_bytes = last ? n : c->reserve_bytes;
+        c->job.job_bytes = last ? n : c->reserve_bytes;
         c->reserve_bytes = 0;
     }
     HIP_TRY(hipEventRecord(c->h2d_ev[0], cs));
@@ -797,66 +705,58 @@ static int ingest_impl(fk_ctx *c, const uint8_t *fasta, size_t n, int last) {
         const size_t nseg = (n + seg - 1) / seg;
         const size_t small_from = n - std::min(n, std::max<size_t>(n / 10, 4 * seg));
         auto seg_len = [&](size_t off) { return std::min(off < small_from ? big : seg, n - off); };
-        while ((c->pm_active || fq) && c->seg_evs.size() < nseg) {
-            hipEvent_t e = nullptr;
-            HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            c->seg_evs.push_back(e);
-        }
+        if (c->job.pm_active || fq) HIP_TRY(ensure_events(c->seg_evs, nseg, hipEventDisableTiming));
         size_t off = 0;
         for (size_t i = 0; off < n; ++i) {
             const size_t len = seg_len(off);
             HIP_TRY(hipMemcpyAsync(dst + off, fasta + off, len, hipMemcpyHostToDevice, cs));
-            if (c->pm_active || fq) HIP_TRY(hipEventRecord(c->seg_evs[i], cs));
+            if (c->job.pm_active || fq) HIP_TRY(hipEventRecord(c->seg_evs[i], cs));
             off += len;
         }
         HIP_TRY(hipEventRecord(c->h2d_ev[1], cs));
         // every segment's map is queued too (one rank; the exchange steps wait on the host between
         // them), then the pieces are staged on the staging stream behind the map of their last
         // segment: the host's waits for a piece's partition never hold back a later map launch
-        while (!pieces && c->pm_active && c->map_evs.size() < nseg) {
-            hipEvent_t e = nullptr;
-            HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            c->map_evs.push_back(e);
-        }
+        if (!pieces && c->job.pm_active) HIP_TRY(ensure_events(c->map_evs, nseg, hipEventDisableTiming));
         c->seg_tiles.clear();
         off = 0;
-        for (size_t i = 0; (c->pm_active || fq) && off < n; ++i) {
+        for (size_t i = 0; (c->job.pm_active || fq) && off < n; ++i) {
             off += seg_len(off);
             HIP_TRY(hipStreamWaitEvent(s, c->seg_evs[i], 0));
             uint64_t limit = have + off;
             if (fq) FK_TRY(fq_advance(c, fasta, have, off, last && off == n, &limit));
-            if (!c->pm_active) continue;
+            if (!c->job.pm_active) continue;
             FK_TRY(premap_launch(c, limit, last && off == n));
             if (pieces) {
                 FK_TRY(xch_maybe_piece(c));
             } else {
                 HIP_TRY(hipEventRecord(c->map_evs[i], s));
-                c->seg_tiles.push_back(c->pm_tiles);
+                c->seg_tiles.push_back(c->job.pm_tiles);
             }
         }
-        for (size_t i = 0; !pieces && c->pm_active && i < c->seg_tiles.size(); ++i)
+        for (size_t i = 0; !pieces && c->job.pm_active && i < c->seg_tiles.size(); ++i)
             FK_TRY(local_maybe_piece(c, c->seg_tiles[i], c->map_evs[i]));
     } else {
         size_t off = 0;
         for (int i = 0; off < n; ++i) {
             const size_t len = std::min(PIN_CHUNK, n - off);
             HIP_TRY(hipEventSynchronize(c->pin_ev[i & 1]));  // its previous DMA is done
-            memcpy(c->pinned[i & 1], fasta + off, len);
-            HIP_TRY(hipMemcpyAsync(dst + off, c->pinned[i & 1], len, hipMemcpyHostToDevice, cs));
+            memcpy(c->pinned[i & 1].p, fasta + off, len);
+            HIP_TRY(hipMemcpyAsync(dst + off, c->pinned[i & 1].p, len, hipMemcpyHostToDevice, cs));
             HIP_TRY(hipEventRecord(c->pin_ev[i & 1], cs));
             off += len;
-            if (c->pm_active || fq) {
+            if (c->job.pm_active || fq) {
                 HIP_TRY(hipEventRecord(c->seg_ev, cs));
                 HIP_TRY(hipStreamWaitEvent(s, c->seg_ev, 0));
                 uint64_t limit = have + off;
                 if (fq) FK_TRY(fq_advance(c, fasta, have, off, last && off == n, &limit));
-                if (!c->pm_active) continue;
+                if (!c->job.pm_active) continue;
                 FK_TRY(premap_launch(c, limit, last && off == n));
                 if (pieces) {
                     FK_TRY(xch_maybe_piece(c));
                 } else {
                     HIP_TRY(hipEventRecord(c->seg_ev, s));  // reused: the staging stream waits on it at once
-                    FK_TRY(local_maybe_piece(c, c->pm_tiles, c->seg_ev));
+                    FK_TRY(local_maybe_piece(c, c->job.pm_tiles, c->seg_ev));
                 }
             }
         }
@@ -866,21 +766,21 @@ static int ingest_impl(fk_ctx *c, const uint8_t *fasta, size_t n, int last) {
         uint64_t limit = 0;
         if (last && n == 0) FK_TRY(fq_advance(c, fasta, have, 0, true, &limit));  // the input ends here
         // the caller's bytes behind the frontier, for the next call's look at the record they begin
-        const uint64_t tb = have - c->fq_tail.size();
+        const uint64_t tb = have - c->job.fq_tail.size();
         std::vector<uint8_t> tail;
-        if (c->fq_done < have) tail.assign(c->fq_tail.begin() + (c->fq_done - tb), c->fq_tail.end());
-        const uint64_t from = c->fq_done > have ? c->fq_done - have : 0;
+        if (c->job.fq_done < have) tail.assign(c->job.fq_tail.begin() + (c->job.fq_done - tb), c->job.fq_tail.end());
+        const uint64_t from = c->job.fq_done > have ? c->job.fq_done - have : 0;
         if (from < n) tail.insert(tail.end(), fasta + from, fasta + n);
-        c->fq_tail.swap(tail);
+        c->job.fq_tail.swap(tail);
     }
-    if (c->pm_active && last) {
-        c->pm_last_seen = true;
+    if (c->job.pm_active && last) {
+        c->job.pm_last_seen = true;
         if (n == 0) FK_TRY(premap_launch(c, need, true));
     }
     HIP_TRY(hipStreamSynchronize(cs));  // the source has been read
     c->ms_h2d = ev_ms(c->h2d_ev[0], c->h2d_ev[1]);
     c->n_fasta = need;
-    reset_results(c);
+    reset_results(c);  // an appending call too
     return FK_OK;
 }
 
@@ -1033,19 +933,15 @@ FK_EXPORT int fk_ingest_device(fk_ctx *c, const void *d, size_t n, int last) {
 static int ingest_device_impl(fk_ctx *c, const void *d, size_t n, int last) {
     if (!d && n) return set_err(FK_E_INVALID, "null argument");
     DeviceGuard dg_(c->device);
-    if (c->comm && c->xch.open) return set_err(FK_E_STATE, "fk_ingest_device: the previous job's exchange is unfinished");
-    if (c->comm) xch_reset(c);
-    c->dev_open = last == 0;  // a borrowed input takes no appended host chunks
+    if (c->comm && c->job.xch.open) return set_err(FK_E_STATE, "fk_ingest_device: the previous job's exchange is unfinished");
     c->ingest_fresh = true;
-    c->pm_active = false;
-    pieces_reset(c);
-    reset_results(c);
-    FK_TRY(fq_begin_job(c, c->in_format == FK_FORMAT_FASTQ));
-    if (c->fq_job) {
+    FK_TRY(begin_job(c, c->in_format == FK_FORMAT_FASTQ));
+    c->job.dev_open = last == 0;  // a borrowed input takes no appended host chunks
+    if (c->job.fq_job) {
         // the borrowed buffer stays as it is: the stage copies it into fasta_own as it reads it
         FK_TRY(ensure(c->fasta_own, n));
         FK_TRY(fq_normalise(c, (const uint8_t *)d, 0, n, true));
-        c->fq_done = n;
+        c->job.fq_done = n;
         c->d_fasta = c->fasta_own.as<uint8_t>();
     } else if (((uintptr_t)d & 15) != 0) {
         FK_TRY(ensure(c->fasta_own, n));
@@ -1075,18 +971,13 @@ FK_EXPORT int fk_synth_fasta_device(fk_ctx *c, uint64_t first_read, uint64_t n_r
     const SynthParams p = make_synth(first_read, n_reads, read_len, genome_len, seed, err_rate, n_rate);
     const uint64_t nb = n_reads * p.rec_bytes;
     FK_TRY(ensure(c->fasta_own, nb));
-    if (c->comm && c->xch.open) return set_err(FK_E_STATE, "fk_synth_fasta_device: the previous job's exchange is unfinished");
-    if (c->comm) xch_reset(c);
+    if (c->comm && c->job.xch.open) return set_err(FK_E_STATE, "fk_synth_fasta_device: the previous job's exchange is unfinished");
     HIP_TRY(launch_synth(c->fasta_own.as<uint8_t>(), nb, p, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->dev_open = false;
     c->ingest_fresh = true;
-    c->pm_active = false;
-    pieces_reset(c);
-    FK_TRY(fq_begin_job(c, false));  // synthetic FASTA, whatever the context's format
+    FK_TRY(begin_job(c, false));  // synthetic FASTA, whatever the context's format
     c->d_fasta = c->fasta_own.as<uint8_t>();
     c->n_fasta = nb;
-    reset_results(c);
     return FK_OK;
 }
 
@@ -1155,14 +1046,11 @@ static int map_records(fk_ctx *c) {
     const double t_start = now_ms();
     hipStream_t s = c->stream;
     c->ingest_fresh = true;  // a later fk_ingest starts a new input
-    c->dev_open = false;
+    c->job.dev_open = false;
     const uint64_t n = c->d_fasta ? c->n_fasta : 0;
-    reset_results(c);
-    c->stats = fk_stats{};
+    new_result(c);
     c->stats.fasta_bytes = n;
-    c->nrec = c->nkmers = 0;
-    c->rec_tiled = false;
-    c->job_open = false;
+    c->job.job_open = false;
     // FASTQ: what is left behind the frontier ends the input; the stage's counters and its malformed
     // flag come back with the map's own read-back below (every path with input waits on the stream)
     FK_TRY(fq_finish_pending(c, n));
@@ -1172,10 +1060,10 @@ static int map_records(fk_ctx *c) {
     // two-kernel path below maps the inputs the fused kernel hands back
     bool fused_ok = false;
     c->stats.ms_h2d = c->ms_h2d;
-    if (c->pm_active && n) {
+    if (c->job.pm_active && n) {
         // streamed map (fk_ingest launched the tiles as their bytes landed)
-        if (!c->pm_last_seen) FK_TRY(premap_launch(c, n, true));  // the input ends here
-        HIP_TRY(launch_tile_totals(c->tcnt.as<uint32_t>(), c->tstat.as<uint32_t>(), c->pm_tiles,
+        if (!c->job.pm_last_seen) FK_TRY(premap_launch(c, n, true));  // the input ends here
+        HIP_TRY(launch_tile_totals(c->tcnt.as<uint32_t>(), c->tstat.as<uint32_t>(), c->job.pm_tiles,
                                    c->counters.as<unsigned long long>(), s));
         uint64_t h[4] = {0, 0, 0, 0};
         HIP_TRY(hipMemcpyAsync(h, c->counters.p, 32, hipMemcpyDeviceToHost, s));
@@ -1184,7 +1072,7 @@ static int map_records(fk_ctx *c) {
         if (!h[2]) {
             fused_ok = true;
             c->rec_tiled = true;
-            c->rec_tiles = c->pm_tiles;
+            c->rec_tiles = c->job.pm_tiles;
             c->nrec = h[0];
             c->nkmers = h[1];
             c->stats.positions = h[3];
@@ -1193,11 +1081,11 @@ static int map_records(fk_ctx *c) {
             c->stats.ms_signature = ev_ms(c->ev[10], c->ev[11]);
             c->stats.ms_signature_kernel = c->stats.ms_signature;
         }
-        c->pm_active = false;
+        c->job.pm_active = false;
     } else if (c->fused && n && map_fused_supported(c->cfg.k, c->cfg.m, (uint32_t)c->Bc)) {
         FK_TRY(map_fused(c, n, &fused_ok));
     }
-    c->pm_active = false;
+    c->job.pm_active = false;
 
     const uint64_t ntiles = (n + ENC_TILE - 1) / ENC_TILE;
     const uint64_t code_words = n / 16 + 2 * POS_PAD_WORDS + 512;
@@ -1314,7 +1202,7 @@ FK_EXPORT int fk_map(fk_ctx *c, uint64_t *send_counts) {
     if (!c) return set_err(FK_E_INVALID, "null ctx");
     DeviceGuard dg_(c->device);
     // one rank: the pieces staged during fk_ingest read the mapped tiles on the staging stream
-    if (c->st_np && !c->comm) HIP_TRY(hipStreamWaitEvent(c->stream, c->xstage_ev, 0));
+    if (c->job.st_np && !c->comm) HIP_TRY(hipStreamWaitEvent(c->stream, c->xstage_ev, 0));
     FK_TRY(map_records(c));
     const double t_start = now_ms();
     hipStream_t s = c->stream;
@@ -1402,7 +1290,7 @@ FK_EXPORT int fk_lpt_owners(const uint64_t *sizes, int32_t nbins, int32_t nranks
 FK_EXPORT int fk_set_bin_owners(fk_ctx *c, const int32_t *owner, uint64_t *send_counts) {
     if (!c || !owner) return set_err(FK_E_INVALID, "null argument");
     DeviceGuard dg_(c->device);
-    if (c->comm && c->xch.open) return set_err(FK_E_STATE, "fk_set_bin_owners inside a job's exchange");
+    if (c->comm && c->job.xch.open) return set_err(FK_E_STATE, "fk_set_bin_owners inside a job's exchange");
     for (int32_t b = 0; b < c->Bc; ++b)
         if (owner[b] < 0 || (uint32_t)owner[b] >= c->G)
             return set_err(FK_E_INVALID, "owner[%d] = %d is not a rank of %u", b, owner[b], c->G);
@@ -2278,25 +2166,11 @@ FK_EXPORT int fk_reduce_grouped(fk_ctx *c, const void *d_recv, uint64_t nrecv, c
 // staged pieces: a job's input partitioned and expanded piece by piece while later pieces land
 // ---------------------------------------------------------------------------
 
-static void pieces_reset(fk_ctx *c) {
-    c->st_np = 0;
-    c->st_cut = 0;
-    c->st_kmers = 0;
-    c->pieces_void = false;
-    c->tiles_counted = 0;
-    c->segs_counted = 0;
-    c->fold_decided = c->fold_on = false;
-    c->fold_sample_ppm = 0;
-    c->fold_in = 0;
-    c->fold_pieces.clear();
-    c->st_weighted = false;
-}
-
 // Staged pieces per job: 128-bit keys at most STAGE_MAXP128 (their kernels' piece loops stop there)
 static uint32_t stage_maxp(const fk_ctx *c) { return c->KW == 2 ? (uint32_t)STAGE_MAXP128 : (uint32_t)STAGE_MAXP; }
 // one rank's piece ends: FASTKMER_PIECE_CUTS, five pieces for a 64-bit job of >= 4 GB, else four
 static const std::vector<double> &local_cuts(const fk_ctx *c) {
-    if (!c->cuts_env && c->KW == 1 && c->job_bytes >= (4ull << 30) && STAGE_MAXP >= 5) return c->st_cuts5;
+    if (!c->cuts_env && c->KW == 1 && c->job.job_bytes >= (4ull << 30) && STAGE_MAXP >= 5) return c->st_cuts5;
     return c->st_cuts;
 }
 
@@ -2314,22 +2188,22 @@ static bool staged_eligible(const fk_ctx *c) { return staged_ok(c) && c->G == 1 
 static int staged_expand_chunks(fk_ctx *c, StreamWs on, hipStream_t cut, uint32_t nchunks,
                                 const std::vector<uint64_t> &bkm, double frac) {
     hipStream_t s = on.s;
-    const uint32_t p = c->st_np;
+    const uint32_t p = c->job.st_np;
     uint64_t pk = 0, maxb = 0;
     for (uint64_t v : bkm) pk += v, maxb = std::max(maxb, v);
     if (pk == 0) return FK_OK;  // nothing to expand (the piece's records hold no k-mers)
     if (p == 0) {
         const double scale = frac > 0.0 ? std::max(1.0, 1.0 / frac) : 2.0;
-        c->st_plan = sorted_plan(c, (uint64_t)((double)maxb * scale));
-        if (!c->st_plan.tiered || !c->st_plan.two_level)
+        c->job.st_plan = sorted_plan(c, (uint64_t)((double)maxb * scale));
+        if (!c->job.st_plan.tiered || !c->job.st_plan.two_level)
             return set_err(FK_E_STATE, "staged pieces need the tiered two-level count");
     }
     // every piece takes both levels (level 2 sizes its workgroups to the keys per super-cell: a 15 %
     // piece 0.75 ms against 1.14 for a one-pass scatter)
-    SortedPlan pl = c->st_plan;
+    SortedPlan pl = c->job.st_plan;
     HIP_TRY(hipEventRecord(c->st_ev[4 * p + 2], s));
     FK_TRY(sorted_expand(c, on, cut, pl, nchunks, pk, c->st_keys[p], c->st_cb[p]));
-    const uint64_t ncell_all = (uint64_t)c->nlb << c->st_plan.F;
+    const uint64_t ncell_all = (uint64_t)c->nlb << c->job.st_plan.F;
     FK_TRY(ensure(c->st_total, ncell_all * 8));
     if (cut) {  // the job's cell totals on the cut's stream, while this piece is expanded
         HIP_TRY(hipStreamWaitEvent(cut, c->side_ev[2], 0));
@@ -2338,15 +2212,15 @@ static int staged_expand_chunks(fk_ctx *c, StreamWs on, hipStream_t cut, uint32_
         HIP_TRY(launch_add_u64(c->st_total.as<uint64_t>(), c->cell_total.as<uint64_t>(), ncell_all, p == 0, s));
     }
     HIP_TRY(hipEventRecord(c->st_ev[4 * p + 3], s));
-    c->st_kmers += pk;
-    c->st_np = p + 1;
+    c->job.st_kmers += pk;
+    c->job.st_np = p + 1;
     htrace("staged: piece expanded");
     return FK_OK;
 }
 
 // One rank: partitions a piece of the mapped tiles by local bin, then expands it.
 static int staged_expand(fk_ctx *c, StreamWs on, hipStream_t cut, const RecSrc &src, double frac) {
-    const uint32_t p = c->st_np;
+    const uint32_t p = c->job.st_np;
     if (p >= stage_maxp(c)) return set_err(FK_E_STATE, "more than %u staged pieces", stage_maxp(c));
     uint64_t nrecv = 0;
     std::vector<Chunk> chunks;
@@ -2363,7 +2237,7 @@ static int staged_count(fk_ctx *c, hipStream_t cut) {
     const double t0 = now_ms();
     const StreamWs on = c->main_on();
     hipStream_t s = on.s;
-    const SortedPlan pl = c->st_plan;
+    const SortedPlan pl = c->job.st_plan;
     const uint32_t nlb = c->nlb;
     const uint64_t ncell_all = (uint64_t)nlb << pl.F;
     HIP_TRY(hipEventRecord(c->ev[6], s));
@@ -2375,25 +2249,25 @@ static int staged_count(fk_ctx *c, hipStream_t cut) {
     HIP_TRY(scan_excl_sum_u64(c->cell_total.as<uint64_t>(), c->cell_base.as<uint64_t>(), ncell_all,
                               c->cell_base.as<uint64_t>() + ncell_all, *on.ws, cs));
     BucketSrc src{nullptr, pl.F};
-    src.np = (int)c->st_np;
-    src.weighted = !c->fold_pieces.empty() || c->st_weighted;
-    c->last_np = c->st_np, c->last_cells = ncell_all;
-    for (uint32_t p = 0; p < c->st_np; ++p) {
+    src.np = (int)c->job.st_np;
+    src.weighted = !c->job.fold_pieces.empty() || c->job.st_weighted;
+    c->last_np = c->job.st_np, c->last_cells = ncell_all;
+    for (uint32_t p = 0; p < c->job.st_np; ++p) {
         src.pk[p] = c->st_keys[p].as<uint64_t>();
         src.pcb[p] = c->st_cb[p].as<uint64_t>();
     }
-    FK_TRY(sorted_count(c, on, cut, pl, src, c->st_kmers));
+    FK_TRY(sorted_count(c, on, cut, pl, src, c->job.st_kmers));
     HIP_TRY(hipEventRecord(c->ev[7], s));
     FK_TRY(read_bin_offsets(c, s));
     htrace("staged: bin offsets read");
     double mp = 0.0, mx = 0.0;
-    for (uint32_t p = 0; p < c->st_np; ++p) {
+    for (uint32_t p = 0; p < c->job.st_np; ++p) {
         mp += ev_ms(c->st_ev[4 * p], c->st_ev[4 * p + 1]);
         mx += ev_ms(c->st_ev[4 * p + 2], c->st_ev[4 * p + 3]);
     }
     c->stats.ms_partition = mp;
     c->stats.ms_count = mx + ev_ms(c->ev[6], c->ev[7]);
-    c->stats.pieces_counted = c->st_np;
+    c->stats.pieces_counted = c->job.st_np;
     count_done(c, c->nrec, t0);
     return FK_OK;
 }
@@ -2407,16 +2281,16 @@ static int staged_count(fk_ctx *c, hipStream_t cut) {
 // most stage_maxp - 1).
 static bool local_piece_due(const fk_ctx *c, uint64_t tiles) {
     constexpr uint64_t MIN_PIECE = 256ull << 20;  // a piece holds >= half of it
-    if (c->st_np >= stage_maxp(c) - 1) return false;
+    if (c->job.st_np >= stage_maxp(c) - 1) return false;
     const uint64_t tile = fm_tile_bytes(FUSED_NT);
-    if (c->job_bytes && !c->piece_bytes_set) {
+    if (c->job.job_bytes && !c->piece_bytes_set) {
         const std::vector<double> &cuts = local_cuts(c);
-        if (c->job_bytes < 2 * MIN_PIECE || c->st_cut >= cuts.size()) return false;
-        const uint64_t end = (uint64_t)(cuts[c->st_cut] * (double)c->job_bytes);
-        return tiles * tile >= end && (tiles - c->tiles_counted) * tile >= MIN_PIECE / 2;
+        if (c->job.job_bytes < 2 * MIN_PIECE || c->job.st_cut >= cuts.size()) return false;
+        const uint64_t end = (uint64_t)(cuts[c->job.st_cut] * (double)c->job.job_bytes);
+        return tiles * tile >= end && (tiles - c->job.tiles_counted) * tile >= MIN_PIECE / 2;
     }
     // every piece_bytes: at most four pieces (three before fk_finish), as the exchange's
-    return c->st_np < 3 && (tiles - c->tiles_counted) * tile >= c->piece_bytes;
+    return c->job.st_np < 3 && (tiles - c->job.tiles_counted) * tile >= c->piece_bytes;
 }
 
 // ---- the fold of a landed piece (fk_fold.inc)
@@ -2436,10 +2310,10 @@ constexpr uint32_t FOLD_SAMPLE_STRIDE = 61;
 constexpr uint64_t FOLD_SAMPLE_MAX = 4096;
 constexpr uint64_t FOLD_MAX_PPM = 600000;
 static int fold_decide(fk_ctx *c, StreamWs on, uint32_t p) {
-    c->fold_decided = true;
-    c->fold_on = c->fold_mode == 2;
+    c->job.fold_decided = true;
+    c->job.fold_on = c->fold_mode == 2;
     if (c->fold_mode != 1) return FK_OK;
-    const SortedPlan &pl = c->st_plan;
+    const SortedPlan &pl = c->job.st_plan;
     FK_TRY(ensure(c->fold_io, 16));
     const uint64_t nsc = (uint64_t)c->nlb << pl.F1;
     const uint32_t stride = (uint32_t)std::max<uint64_t>(FOLD_SAMPLE_STRIDE, (nsc / FOLD_SAMPLE_MAX) | 1ull);
@@ -2449,8 +2323,8 @@ static int fold_decide(fk_ctx *c, StreamWs on, uint32_t p) {
     uint64_t io[2] = {0, 0};
     HIP_TRY(hipMemcpyAsync(io, c->fold_io.p, 16, hipMemcpyDeviceToHost, on.s));
     HIP_TRY(hipStreamSynchronize(on.s));
-    c->fold_sample_ppm = io[0] ? io[1] * 1000000ull / io[0] : 1000000ull;
-    c->fold_on = io[0] && c->fold_sample_ppm <= FOLD_MAX_PPM;
+    c->job.fold_sample_ppm = io[0] ? io[1] * 1000000ull / io[0] : 1000000ull;
+    c->job.fold_on = io[0] && c->job.fold_sample_ppm <= FOLD_MAX_PPM;
     htrace("staged: fold sampled");
     return FK_OK;
 }
@@ -2459,11 +2333,11 @@ static int fold_decide(fk_ctx *c, StreamWs on, uint32_t p) {
 // the sample's entries per million keys.  counted = false: the pieces were dropped (counted whole).
 static void fold_report(fk_ctx *c, bool counted) {
     uint64_t out = 0;
-    for (uint32_t p : c->fold_pieces) out += c->fold_pin.as<uint64_t>()[p];
-    c->fold_last[0] = counted ? c->fold_pieces.size() : 0;
-    c->fold_last[1] = counted ? c->fold_in : 0;
+    for (uint32_t p : c->job.fold_pieces) out += c->fold_pin.as<uint64_t>()[p];
+    c->fold_last[0] = counted ? c->job.fold_pieces.size() : 0;
+    c->fold_last[1] = counted ? c->job.fold_in : 0;
     c->fold_last[2] = counted ? out : 0;
-    c->fold_last[3] = c->fold_sample_ppm;
+    c->fold_last[3] = c->job.fold_sample_ppm;
 }
 
 // Which pieces of a folding job (staged by local_maybe_piece, st_cut counting this one): with
@@ -2474,7 +2348,7 @@ static void fold_report(fk_ctx *c, bool counted) {
 // was meant to shorten (profiles/r07_fold_c2_timeline_all_pieces.txt: the last piece 4.4 ms late).
 static bool fold_piece_due(const fk_ctx *c) {
     if (c->fold_mode == 2) return true;
-    if (c->job_bytes && !c->piece_bytes_set) return c->st_cut == 1;
+    if (c->job.job_bytes && !c->piece_bytes_set) return c->job.st_cut == 1;
     return true;
 }
 
@@ -2484,7 +2358,7 @@ static bool fold_piece_due(const fk_ctx *c) {
 // The piece's raw k-mer count stays an upper bound of its entries wherever a size is needed.
 static int fold_piece(fk_ctx *c, StreamWs on, uint32_t p, uint64_t pk) {
     if (pk == 0 || pk >= (1ull << 32)) return FK_OK;  // u32 entries per cell
-    const SortedPlan &pl = c->st_plan;
+    const SortedPlan &pl = c->job.st_plan;
     const uint64_t ncell_all = (uint64_t)c->nlb << pl.F;
     FK_TRY(ensure(c->fold_cnt, ncell_all * 4));
     FK_TRY(ensure(c->fold_cb, (ncell_all + 1) * 8));
@@ -2500,8 +2374,8 @@ static int fold_piece(fk_ctx *c, StreamWs on, uint32_t p, uint64_t pk) {
     HIP_TRY(hipMemcpyAsync(c->fold_pin.as<uint64_t>() + p, c->fold_cb.as<uint64_t>() + ncell_all, 8,
                            hipMemcpyDeviceToHost, on.s));
     std::swap(c->st_cb[p], c->fold_cb);  // stream order: the raw offsets are overwritten by the next fold's scan
-    c->fold_in += pk;
-    c->fold_pieces.push_back(p);
+    c->job.fold_in += pk;
+    c->job.fold_pieces.push_back(p);
     htrace("staged: piece folded");
     return FK_OK;
 }
@@ -2509,7 +2383,7 @@ static int fold_piece(fk_ctx *c, StreamWs on, uint32_t p, uint64_t pk) {
 // tiles: the tiles mapped once `mapped` (recorded on the map stream) has passed.  The piece is
 // partitioned and expanded on the staging stream, which fk_finish joins (xstage_ev).
 static int local_maybe_piece(fk_ctx *c, uint64_t tiles, hipEvent_t mapped) {
-    if (!staged_eligible(c) || c->pieces_void || !local_piece_due(c, tiles)) return FK_OK;
+    if (!staged_eligible(c) || c->job.pieces_void || !local_piece_due(c, tiles)) return FK_OK;
     const StreamWs on = c->stage_on();
     hipStream_t s = on.s;
     HIP_TRY(hipStreamWaitEvent(s, mapped, 0));
@@ -2517,21 +2391,21 @@ static int local_maybe_piece(fk_ctx *c, uint64_t tiles, hipEvent_t mapped) {
     HIP_TRY(hipMemcpyAsync(h, c->counters.p, 32, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (h[2]) {
-        c->pieces_void = true;
+        c->job.pieces_void = true;
         return FK_OK;
     }
-    const uint64_t t0 = c->tiles_counted, nt = tiles - t0;
+    const uint64_t t0 = c->job.tiles_counted, nt = tiles - t0;
     const RecSrc src = fused_src(c, t0, nt, nt * map_fused_tcap());
-    c->tiles_counted = tiles;
-    c->st_cut += 1;
-    const uint32_t p = c->st_np;
-    const uint64_t k0 = c->st_kmers;
+    c->job.tiles_counted = tiles;
+    c->job.st_cut += 1;
+    const uint32_t p = c->job.st_np;
+    const uint64_t k0 = c->job.st_kmers;
     FK_TRY(staged_expand(c, on, nullptr, src,
-                         c->job_bytes ? (double)(nt * fm_tile_bytes(FUSED_NT)) / (double)c->job_bytes : 0.0));
+                         c->job.job_bytes ? (double)(nt * fm_tile_bytes(FUSED_NT)) / (double)c->job.job_bytes : 0.0));
     // a piece staged here is never the job's last (fk_finish stages that one): fold it while the rest lands
-    if (c->st_np > p && fold_eligible(c)) {
-        if (!c->fold_decided) FK_TRY(fold_decide(c, on, p));
-        if (c->fold_on && fold_piece_due(c)) FK_TRY(fold_piece(c, on, p, c->st_kmers - k0));
+    if (c->job.st_np > p && fold_eligible(c)) {
+        if (!c->job.fold_decided) FK_TRY(fold_decide(c, on, p));
+        if (c->job.fold_on && fold_piece_due(c)) FK_TRY(fold_piece(c, on, p, c->job.st_kmers - k0));
     }
     HIP_TRY(hipEventRecord(c->xstage_ev, s));
     return FK_OK;
@@ -2586,10 +2460,6 @@ FK_EXPORT int fk_exchange_plan(int32_t n_ranks, int32_t parts, const uint64_t *s
     return FK_OK;
 }
 
-static void xch_reset(fk_ctx *c) {
-    c->xch = fk_ctx::Xch{};
-}
-
 // FK_E_NOMEM from an exported call: the message names what the context holds on the device, largest
 // first, so an oversized job shows which of its arrays to size (or free) without a re-run.
 static int note_held(fk_ctx *c, int rc) {
@@ -2629,13 +2499,9 @@ static int comm_fail(fk_ctx *c, int rc) {
 }
 
 static hipEvent_t xch_event(fk_ctx *c, size_t i) {
-    while (c->xev.size() <= i) {
-        hipEvent_t e = nullptr;
-        if (hipEventCreate(&e) != hipSuccess) {
-            (void)hipGetLastError();
-            return nullptr;
-        }
-        c->xev.push_back(e);
+    if (ensure_events(c->xev, i + 1) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
     }
     return c->xev[i];
 }
@@ -2661,12 +2527,12 @@ static int xch_step(fk_ctx *c, const RecSrc *src, uint64_t flags) {
     }
     if (piece_rec) {
         // send ring: earlier pieces are read by the comm stream; wrap around once it has drained
-        if ((c->xch.send_used + piece_rec) * rb > c->xsend.bytes) {
+        if ((c->job.xch.send_used + piece_rec) * rb > c->xsend.bytes) {
             FK_TRY(comm_sync(c, cs));
-            c->xch.send_used = 0;
+            c->job.xch.send_used = 0;
             FK_TRY(ensure(c->xsend, piece_rec * rb * 2));
         }
-        FK_TRY(part_scatter(c->dest, 0, G, c->grp_table.as<uint32_t>(), c->xsend.as<uint64_t>() + c->xch.send_used * c->W,
+        FK_TRY(part_scatter(c->dest, 0, G, c->grp_table.as<uint32_t>(), c->xsend.as<uint64_t>() + c->job.xch.send_used * c->W,
                             s));
         HIP_TRY(hipEventRecord(c->emit_ev, s));
     }
@@ -2680,59 +2546,59 @@ static int xch_step(fk_ctx *c, const RecSrc *src, uint64_t flags) {
     }
     std::string err;
     if (c->comm->alltoall_u64(out.data(), in.data(), msg, cs, err))
-        return set_err(FK_E_COMM, "exchange step %llu, counts: %s", (unsigned long long)c->xch.pieces, err.c_str());
+        return set_err(FK_E_COMM, "exchange step %llu, counts: %s", (unsigned long long)c->job.xch.pieces, err.c_str());
     std::vector<uint64_t> soff(G), sbytes(G), roff(G), rbytes(G);
     bool all_final = false;
     FK_TRY(plan_step(G, L, out.data(), in.data(), rb, soff.data(), sbytes.data(), roff.data(), rbytes.data(), &all_final));
     uint64_t recv_rec = 0;
     for (uint32_t r = 0; r < G; ++r) recv_rec += rbytes[r] / rb;
-    if ((c->xch.recv_used + recv_rec) * rb > c->xrecv.bytes) {
+    if ((c->job.xch.recv_used + recv_rec) * rb > c->xrecv.bytes) {
         // the received records stay until the count: grow, keeping them (sized for the whole input
         // once the first pieces show the records per FASTA byte)
-        uint64_t want = c->xch.recv_used + recv_rec;
-        if (c->xch.expect_bytes && c->xch.tiles_sent) {
-            const double covered = (double)c->xch.tiles_sent * (double)fm_tile_bytes(FUSED_NT);
-            want = std::max<uint64_t>(want, (uint64_t)((double)want * (double)c->xch.expect_bytes / covered * 1.1));
+        uint64_t want = c->job.xch.recv_used + recv_rec;
+        if (c->job.xch.expect_bytes && c->job.xch.tiles_sent) {
+            const double covered = (double)c->job.xch.tiles_sent * (double)fm_tile_bytes(FUSED_NT);
+            want = std::max<uint64_t>(want, (uint64_t)((double)want * (double)c->job.xch.expect_bytes / covered * 1.1));
         }
         FK_TRY(comm_sync(c, cs));
         FK_TRY(comm_sync(c, c->xstage));  // staged expansions may still read the old buffer
-        FK_TRY(grow_keep(c->xrecv, want * rb, c->xch.recv_used * rb, s));
+        FK_TRY(grow_keep(c->xrecv, want * rb, c->job.xch.recv_used * rb, s));
     }
-    const size_t step = (size_t)c->xch.pieces;
+    const size_t step = (size_t)c->job.xch.pieces;
     hipEvent_t e0 = xch_event(c, 2 * step), e1 = xch_event(c, 2 * step + 1);
     if (!e0 || !e1) return set_err(FK_E_DEVICE, "hipEventCreate failed");
     if (piece_rec) HIP_TRY(hipStreamWaitEvent(cs, c->emit_ev, 0));
     HIP_TRY(hipEventRecord(e0, cs));
-    if (c->comm->alltoallv(c->xsend.as<uint8_t>() + c->xch.send_used * rb, soff.data(), sbytes.data(),
-                           c->xrecv.as<uint8_t>() + c->xch.recv_used * rb, roff.data(), rbytes.data(), cs, err))
+    if (c->comm->alltoallv(c->xsend.as<uint8_t>() + c->job.xch.send_used * rb, soff.data(), sbytes.data(),
+                           c->xrecv.as<uint8_t>() + c->job.xch.recv_used * rb, roff.data(), rbytes.data(), cs, err))
         return set_err(FK_E_COMM, "exchange step %llu, records: %s", (unsigned long long)step, err.c_str());
     HIP_TRY(hipEventRecord(e1, cs));
     for (uint32_t r = 0; r < G; ++r) {
         const uint64_t *m = in.data() + (size_t)r * msg;
         if (m[2 * L] & XF_RETRACT) {  // the sender mapped again from scratch: its earlier pieces are void
-            c->pieces_void = true;      // (and so are the piece counts that hold them)
-            auto &v = c->xch.segs;
+            c->job.pieces_void = true;      // (and so are the piece counts that hold them)
+            auto &v = c->job.xch.segs;
             v.erase(std::remove_if(v.begin(), v.end(), [&](const fk_ctx::XSeg &g) { return g.sender == (int32_t)r; }),
                     v.end());
         }
         if (!rbytes[r]) continue;
         fk_ctx::XSeg g;
-        g.off = c->xch.recv_used + roff[r] / rb;
+        g.off = c->job.xch.recv_used + roff[r] / rb;
         g.sender = (int32_t)r;
         g.step = step;
         g.rec.assign(m, m + L);
         g.kmer.assign(m + L, m + 2 * L);
-        c->xch.segs.push_back(std::move(g));
-        if (r != (uint32_t)c->cfg.rank) c->xch.bytes_received += rbytes[r];
+        c->job.xch.segs.push_back(std::move(g));
+        if (r != (uint32_t)c->cfg.rank) c->job.xch.bytes_received += rbytes[r];
     }
     for (uint32_t d = 0; d < G; ++d)
-        if (d != (uint32_t)c->cfg.rank) c->xch.bytes_sent += sbytes[d];
-    c->xch.send_used += piece_rec;
-    c->xch.recv_used += recv_rec;
-    c->xch.pieces += 1;
-    c->xch.open = true;
-    c->xch.all_final = all_final;
-    if (flags & XF_FINAL) c->xch.sent_final = true;
+        if (d != (uint32_t)c->cfg.rank) c->job.xch.bytes_sent += sbytes[d];
+    c->job.xch.send_used += piece_rec;
+    c->job.xch.recv_used += recv_rec;
+    c->job.xch.pieces += 1;
+    c->job.xch.open = true;
+    c->job.xch.all_final = all_final;
+    if (flags & XF_FINAL) c->job.xch.sent_final = true;
     return FK_OK;
 }
 
@@ -2745,7 +2611,7 @@ static int segment_ranges(fk_ctx *c, size_t s0, size_t s1, std::vector<std::vect
     bkm.assign(nlb, 0);
     *nrecv = 0;
     for (size_t i = s0; i < s1; ++i) {
-        const fk_ctx::XSeg &g = c->xch.segs[i];
+        const fk_ctx::XSeg &g = c->job.xch.segs[i];
         uint64_t off = g.off;
         for (uint32_t lb = 0; lb < c->grp_nlb; ++lb) {
             const uint64_t n = g.rec[lb];
@@ -2765,20 +2631,20 @@ static int segment_ranges(fk_ctx *c, size_t s0, size_t s1, std::vector<std::vect
 // staged piece (they arrive grouped by local bin: no partition), once the comm stream has
 // delivered them.  `frac` = their estimated fraction of what this rank receives in the job.
 static int xch_stage_segments(fk_ctx *c, size_t s1, double frac) {
-    if (s1 <= c->segs_counted) return FK_OK;
-    const uint32_t p = c->st_np;
+    if (s1 <= c->job.segs_counted) return FK_OK;
+    const uint32_t p = c->job.st_np;
     if (p >= stage_maxp(c)) return set_err(FK_E_STATE, "more than %u staged pieces", stage_maxp(c));
     const StreamWs on = c->stage_on();
     hipStream_t s = on.s;
     // its earlier work (behind earlier steps' transfers) is done: bounded with a communicator
     FK_TRY(comm_sync(c, s));
-    const uint64_t step = c->xch.segs[s1 - 1].step;
+    const uint64_t step = c->job.xch.segs[s1 - 1].step;
     HIP_TRY(hipStreamWaitEvent(s, c->xev[2 * step + 1], 0));
     std::vector<std::vector<std::pair<uint64_t, uint64_t>>> ranges;
     std::vector<uint64_t> bkm;
     uint64_t nrecv = 0;
-    FK_TRY(segment_ranges(c, c->segs_counted, s1, ranges, bkm, &nrecv));
-    c->segs_counted = s1;
+    FK_TRY(segment_ranges(c, c->job.segs_counted, s1, ranges, bkm, &nrecv));
+    c->job.segs_counted = s1;
     std::vector<Chunk> chunks;
     std::vector<uint32_t> bcb;
     build_chunks(c->nlb, ranges, chunks, bcb);
@@ -2792,9 +2658,9 @@ static int xch_stage_segments(fk_ctx *c, size_t s1, double frac) {
 // Received records of this job so far / expected in all (estimated from the share of the input
 // sent so far; 0 when the input's size is unknown).
 static double xch_recv_frac(const fk_ctx *c, uint64_t recs) {
-    if (!c->xch.expect_bytes || !c->xch.tiles_sent || !c->xch.recv_used) return 0.0;
-    const double sent = (double)c->xch.tiles_sent * (double)fm_tile_bytes(FUSED_NT);
-    const double est = (double)c->xch.recv_used * (double)c->xch.expect_bytes / sent;
+    if (!c->job.xch.expect_bytes || !c->job.xch.tiles_sent || !c->job.xch.recv_used) return 0.0;
+    const double sent = (double)c->job.xch.tiles_sent * (double)fm_tile_bytes(FUSED_NT);
+    const double est = (double)c->job.xch.recv_used * (double)c->job.xch.expect_bytes / sent;
     return est > 0.0 ? std::min(1.0, (double)recs / est) : 0.0;
 }
 
@@ -2802,18 +2668,18 @@ static double xch_recv_frac(const fk_ctx *c, uint64_t recs) {
 // of the job (every step when its size is unknown), at most STAGE_MAXP - 1 times before fk_finish.
 static int xch_maybe_stage(fk_ctx *c, size_t s1) {
     // (at most four pieces: the exchange's cuts are xst_cuts)
-    if (c->st_np >= std::min<uint32_t>(stage_maxp(c), 4) - 1 || s1 <= c->segs_counted) return FK_OK;
+    if (c->job.st_np >= std::min<uint32_t>(stage_maxp(c), 4) - 1 || s1 <= c->job.segs_counted) return FK_OK;
     uint64_t recs = 0, before = 0;
     for (size_t i = 0; i < s1; ++i)
-        for (uint64_t n : c->xch.segs[i].rec) (i < c->segs_counted ? before : recs) += n;
+        for (uint64_t n : c->job.xch.segs[i].rec) (i < c->job.segs_counted ? before : recs) += n;
     const double frac = xch_recv_frac(c, recs);
     // a piece ends once the received records reach the next cut of the job (st_cuts, as the local
     // path's pieces): the last piece -- expanded after the last byte -- is the smallest.  (Staging at
     // every quarter left ~30 % of a 6.25 GB rank for fk_finish: 61.7 ms after it against 47.7 for
     // the local path, profiles/r04c_xch_tail.txt.)
     if (frac > 0.0) {
-        if (c->st_np >= (uint32_t)c->xst_cuts.size()) return FK_OK;
-        if (xch_recv_frac(c, before + recs) < c->xst_cuts[c->st_np]) return FK_OK;
+        if (c->job.st_np >= (uint32_t)c->xst_cuts.size()) return FK_OK;
+        if (xch_recv_frac(c, before + recs) < c->xst_cuts[c->job.st_np]) return FK_OK;
     }
     return xch_stage_segments(c, s1, frac);
 }
@@ -2822,24 +2688,24 @@ static int xch_maybe_stage(fk_ctx *c, size_t s1) {
 // map's fallback flag is read first: a flagged input is mapped again in fk_finish and sent
 // whole, retracting the pieces sent so far.
 static int xch_maybe_piece(fk_ctx *c) {
-    if (c->xch.stop_pieces || c->xch.sent_final) return FK_OK;
+    if (c->job.xch.stop_pieces || c->job.xch.sent_final) return FK_OK;
     const uint64_t tile = fm_tile_bytes(FUSED_NT);
-    if ((c->pm_tiles - c->xch.tiles_sent) * tile < c->piece_bytes) return FK_OK;
+    if ((c->job.pm_tiles - c->job.xch.tiles_sent) * tile < c->piece_bytes) return FK_OK;
     uint64_t h[4] = {0, 0, 0, 0};
     HIP_TRY(hipMemcpyAsync(h, c->counters.p, 32, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (h[2]) {
-        c->xch.stop_pieces = true;
+        c->job.xch.stop_pieces = true;
         return FK_OK;
     }
-    const uint64_t t0 = c->xch.tiles_sent, nt = c->pm_tiles - t0;
+    const uint64_t t0 = c->job.xch.tiles_sent, nt = c->job.pm_tiles - t0;
     const RecSrc src = fused_src(c, t0, nt, nt * map_fused_tcap());
-    c->xch.tiles_sent = c->pm_tiles;
+    c->job.xch.tiles_sent = c->job.pm_tiles;
     const int rc = xch_step(c, &src, 0);
     if (rc) return comm_fail(c, rc);
     // the received segments are expanded (staged) on the staging stream as soon as their transfer
     // ends, this step's included, while the map stream goes on
-    if (staged_ok(c) && !c->pieces_void) FK_TRY(xch_maybe_stage(c, c->xch.segs.size()));
+    if (staged_ok(c) && !c->job.pieces_void) FK_TRY(xch_maybe_stage(c, c->job.xch.segs.size()));
     return FK_OK;
 }
 
@@ -2848,12 +2714,12 @@ static int xch_maybe_piece(fk_ctx *c) {
 static int finish_exchange(fk_ctx *c) {
     const double t0 = now_ms();
     hipStream_t s = c->stream, cs = c->comm_stream;
-    const bool pieced = c->xch.tiles_sent > 0;
-    const uint64_t tiles_sent = c->xch.tiles_sent;
+    const bool pieced = c->job.xch.tiles_sent > 0;
+    const uint64_t tiles_sent = c->job.xch.tiles_sent;
     FK_TRY(map_records(c));
     RecSrc src;
     uint64_t flags = XF_FINAL;
-    if (c->rec_tiled && pieced && !c->xch.stop_pieces && tiles_sent <= c->rec_tiles) {
+    if (c->rec_tiled && pieced && !c->job.xch.stop_pieces && tiles_sent <= c->rec_tiles) {
         const uint64_t nt = c->rec_tiles - tiles_sent;
         src = fused_src(c, tiles_sent, nt, nt * map_fused_tcap());
     } else {
@@ -2862,8 +2728,8 @@ static int finish_exchange(fk_ctx *c) {
     }
     c->mapped = true;
     int rc = xch_step(c, &src, flags);
-    const size_t last_step = (size_t)c->xch.pieces - 1;
-    while (!rc && !c->xch.all_final) rc = xch_step(c, nullptr, XF_FINAL);
+    const size_t last_step = (size_t)c->job.xch.pieces - 1;
+    while (!rc && !c->job.xch.all_final) rc = xch_step(c, nullptr, XF_FINAL);
     // every transfer of the job has been posted; the host waits for them here, bounded, so that none
     // of the count's host waits below can block on a peer that died (FK_E_COMM instead)
     if (!rc) rc = comm_sync(c, cs);
@@ -2873,15 +2739,15 @@ static int finish_exchange(fk_ctx *c) {
     HIP_TRY(hipEventRecord(c->xstage_ev, c->xstage));  // and the staged expansions queued so far are done
     HIP_TRY(hipStreamWaitEvent(s, c->xstage_ev, 0));
     uint64_t nrecv = 0;
-    for (const auto &g : c->xch.segs)
+    for (const auto &g : c->job.xch.segs)
         for (uint64_t n : g.rec) nrecv += n;
-    if (c->st_np && !c->pieces_void) {
+    if (c->job.st_np && !c->job.pieces_void) {
         // staged: the segments not yet expanded, then one count over every piece
-        if (c->segs_counted < c->xch.segs.size()) {
+        if (c->job.segs_counted < c->job.xch.segs.size()) {
             uint64_t recs = 0;
-            for (size_t i = c->segs_counted; i < c->xch.segs.size(); ++i)
-                for (uint64_t n : c->xch.segs[i].rec) recs += n;
-            FK_TRY(xch_stage_segments(c, c->xch.segs.size(), nrecv ? (double)recs / (double)nrecv : 0.0));
+            for (size_t i = c->job.segs_counted; i < c->job.xch.segs.size(); ++i)
+                for (uint64_t n : c->job.xch.segs[i].rec) recs += n;
+            FK_TRY(xch_stage_segments(c, c->job.xch.segs.size(), nrecv ? (double)recs / (double)nrecv : 0.0));
             HIP_TRY(hipEventRecord(c->xstage_ev, c->xstage));
             HIP_TRY(hipStreamWaitEvent(s, c->xstage_ev, 0));
         }
@@ -2889,20 +2755,20 @@ static int finish_exchange(fk_ctx *c) {
     } else {
         std::vector<std::vector<std::pair<uint64_t, uint64_t>>> ranges;
         std::vector<uint64_t> bkm;
-        FK_TRY(segment_ranges(c, 0, c->xch.segs.size(), ranges, bkm, &nrecv));
+        FK_TRY(segment_ranges(c, 0, c->job.xch.segs.size(), ranges, bkm, &nrecv));
         FK_TRY(reduce_ranges(c, c->xrecv.as<uint64_t>(), nrecv, ranges, bkm, t0));
     }
-    pieces_reset(c);
+    end_pieces(c);
     // exchange figures (every transfer has completed: the count waited for them)
     double ms = 0.0;
-    for (size_t i = 0; i < (size_t)c->xch.pieces; ++i) ms += ev_ms(c->xev[2 * i], c->xev[2 * i + 1]);
-    c->stats.xch_steps = c->xch.pieces;
-    c->stats.xch_bytes_sent = c->xch.bytes_sent;
-    c->stats.xch_bytes_received = c->xch.bytes_received;
+    for (size_t i = 0; i < (size_t)c->job.xch.pieces; ++i) ms += ev_ms(c->xev[2 * i], c->xev[2 * i + 1]);
+    c->stats.xch_steps = c->job.xch.pieces;
+    c->stats.xch_bytes_sent = c->job.xch.bytes_sent;
+    c->stats.xch_bytes_received = c->job.xch.bytes_received;
     c->stats.ms_exchange = ms;
-    c->stats.ms_exchange_tail = ev_ms(c->xev[2 * last_step], c->xev[2 * ((size_t)c->xch.pieces - 1) + 1]);
+    c->stats.ms_exchange_tail = ev_ms(c->xev[2 * last_step], c->xev[2 * ((size_t)c->job.xch.pieces - 1) + 1]);
     c->stats.records_received = nrecv;
-    xch_reset(c);
+    c->job.xch = fk_ctx::Xch{};
     return FK_OK;
 }
 
@@ -2925,42 +2791,42 @@ static int finish_local(fk_ctx *c) {
                                    "fk_map/fk_map_emit/fk_reduce", c->G);
     FK_TRY(fk_map(c, nullptr));  // joins the staging stream first
     DeviceGuard dg_(c->device);
-    if (c->st_np && c->rec_tiled && !c->pieces_void && c->tiles_counted <= c->rec_tiles) {
+    if (c->job.st_np && c->rec_tiled && !c->job.pieces_void && c->job.tiles_counted <= c->rec_tiles) {
         // staged pieces were expanded while the input landed: the last piece, then one count
         // the job's bucket cut needs the last piece's cell totals, not its keys: it runs on the side
         // stream while the piece's two expansion levels run on `stream`
         int rc = FK_OK;
-        const hipStream_t cut = c->rec_tiles > c->tiles_counted ? c->tier_side : nullptr;
+        const hipStream_t cut = c->rec_tiles > c->job.tiles_counted ? c->tier_side : nullptr;
         // the cut's stream starts after everything queued so far (re-recorded once the last piece's cell
         // offsets are scanned; a piece without k-mers records nothing more)
         if (cut) HIP_TRY(hipEventRecord(c->side_ev[2], c->stream));
-        if (c->rec_tiles > c->tiles_counted) {
-            const uint64_t t0 = c->tiles_counted, nt = c->rec_tiles - t0;
+        if (c->rec_tiles > c->job.tiles_counted) {
+            const uint64_t t0 = c->job.tiles_counted, nt = c->rec_tiles - t0;
             rc = staged_expand(c, c->main_on(), cut, fused_src(c, t0, nt, nt * map_fused_tcap()),
-                               c->job_bytes ? (double)(nt * fm_tile_bytes(FUSED_NT)) / (double)c->job_bytes : 0.0);
+                               c->job.job_bytes ? (double)(nt * fm_tile_bytes(FUSED_NT)) / (double)c->job.job_bytes : 0.0);
         }
         if (rc == FK_OK) rc = staged_count(c, cut);
         if (cut) (void)hipStreamSynchronize(cut);
         FK_TRY(rc);
         fold_report(c, true);
-        pieces_reset(c);
+        end_pieces(c);
         return FK_OK;
     }
     fold_report(c, false);
-    pieces_reset(c);
+    end_pieces(c);
     return reduce_src(c, map_src(c));
 }
 
 static int attach_comm(fk_ctx *c, fk::Comm *comm) {
     DeviceGuard dg_(c->device);
-    if (!c->comm_stream) HIP_TRY(hipStreamCreateWithFlags(&c->comm_stream, hipStreamNonBlocking));
-    if (!c->xstage) HIP_TRY(hipStreamCreateWithFlags(&c->xstage, hipStreamNonBlocking));
-    if (!c->xstage_ev) HIP_TRY(hipEventCreateWithFlags(&c->xstage_ev, hipEventDisableTiming));
-    if (!c->emit_ev) HIP_TRY(hipEventCreateWithFlags(&c->emit_ev, hipEventDisableTiming));
+    HIP_TRY(c->comm_stream.create());
+    HIP_TRY(c->xstage.create());
+    HIP_TRY(c->xstage_ev.create(hipEventDisableTiming));
+    HIP_TRY(c->emit_ev.create(hipEventDisableTiming));
     c->comm = comm;
     if (!c->piece_bytes_set) c->piece_bytes = 1ull << 30;
     FK_TRY(fk_set_grouped_emit(c, 1));  // records leave grouped by (owner rank, local bin)
-    xch_reset(c);
+    c->job.xch = fk_ctx::Xch{};
     return FK_OK;
 }
 
@@ -3030,7 +2896,7 @@ FK_EXPORT int fk_comm_allreduce_u64(fk_ctx *c, uint64_t *v, size_t n) {
 // exchange), the per-bin k-mer totals are summed over the ranks (the reduceByKey of :1024), the
 // LPT placement is computed identically on every rank and installed for the job's exchange.
 static int sample_bin_kmers(fk_ctx *c, const uint8_t *sample, size_t n, std::vector<uint64_t> &sizes) {
-    if (c->comm && c->xch.open) return set_err(FK_E_STATE, "bin placement inside a job's exchange");
+    if (c->comm && c->job.xch.open) return set_err(FK_E_STATE, "bin placement inside a job's exchange");
     sizes.assign((size_t)c->Bc, 0);
     fk::Comm *comm = c->comm;
     c->comm = nullptr;  // the sample is mapped here, never exchanged
@@ -3151,21 +3017,17 @@ FK_EXPORT int fk_debug_comm_hold(fk_ctx *c, int32_t max_seconds) {
     if (!c || max_seconds < 1) return set_err(FK_E_INVALID, "bad argument");
     if (!c->comm) return set_err(FK_E_STATE, "fk_debug_comm_hold needs a communicator (fk_comm_init*)");
     DeviceGuard dg_(c->device);
-    if (!c->hold_flag) {
-        void *p = nullptr;
-        HIP_TRY(hipHostMalloc(&p, 64, hipHostMallocMapped | hipHostMallocCoherent));
-        c->hold_flag = static_cast<uint32_t *>(p);
-    }
-    __atomic_store_n(c->hold_flag, 0u, __ATOMIC_RELEASE);
+    if (!c->hold_flag.p) HIP_TRY(c->hold_flag.alloc(64, hipHostMallocMapped | hipHostMallocCoherent));
+    __atomic_store_n(c->hold_flag.as<uint32_t>(), 0u, __ATOMIC_RELEASE);
     void *dflag = nullptr;
-    HIP_TRY(hipHostGetDevicePointer(&dflag, c->hold_flag, 0));
+    HIP_TRY(hipHostGetDevicePointer(&dflag, c->hold_flag.p, 0));
     // wall-clock ticks of max_seconds: the attribute is in kHz (100 MHz on gfx950); a rate reported
     // below that bounds the hold by 100 MHz ticks instead (longer, never shorter, than asked)
     int khz = 0;
     HIP_TRY(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, c->device));
     const uint64_t ticks = (uint64_t)max_seconds * (uint64_t)std::max(khz, 100000) * 1000ull;
     const hipStream_t cs2 = c->comm->counts_stream();
-    for (hipStream_t st : {c->comm_stream, cs2})
+    for (hipStream_t st : {(hipStream_t)c->comm_stream, cs2})
         if (st) HIP_TRY(launch_hold_stream(static_cast<const uint32_t *>(dflag), ticks, st));
     return FK_OK;
 }
@@ -3186,7 +3048,7 @@ FK_EXPORT int fk_debug_comm_held(fk_ctx *c) {
 
 FK_EXPORT int fk_debug_comm_release(fk_ctx *c) {
     if (!c) return set_err(FK_E_INVALID, "null ctx");
-    if (c->hold_flag) __atomic_store_n(c->hold_flag, 1u, __ATOMIC_RELEASE);
+    if (c->hold_flag.p) __atomic_store_n(c->hold_flag.as<uint32_t>(), 1u, __ATOMIC_RELEASE);
     return FK_OK;
 }
 
@@ -3216,7 +3078,7 @@ static int debug_wave_count(int32_t device, int32_t k, int32_t F, uint32_t c0, u
             return set_err(FK_E_RANGE, "key %u lies outside cells [%u, %u)", i, c0, c1);
     }
     DeviceGuard dg_(device);
-    TempBuf dk, dok, doc, du, db;
+    DevBuf dk, dok, doc, du, db;
     FK_TRY(ensure(dk, (uint64_t)n * 8 * KW));
     FK_TRY(ensure(dok, (uint64_t)n * 8 * KW));
     FK_TRY(ensure(doc, (uint64_t)n * 4));
@@ -3272,7 +3134,7 @@ FK_EXPORT int fk_debug_count_pieces(fk_ctx *c, int32_t F, int32_t np, const uint
     if (!c || !keys || !cell_counts) return set_err(FK_E_INVALID, "null argument");
     const int k = c->cfg.k, KW = c->KW;
     if (!staged_eligible(c)) return set_err(FK_E_INVALID, "staged pieces need k <= 63, one rank and no communicator");
-    if (c->job_open) return set_err(FK_E_STATE, "fk_debug_count_pieces inside a job (after its first fk_ingest)");
+    if (c->job.job_open) return set_err(FK_E_STATE, "fk_debug_count_pieces inside a job (after its first fk_ingest)");
     if (F < 1 || F > std::min(MAX_FINE_BITS, 2 * k)) return set_err(FK_E_INVALID, "F = %d outside 1 .. min(%d, 2k)", F, MAX_FINE_BITS);
     if (np < 1 || (uint32_t)np > stage_maxp(c)) return set_err(FK_E_INVALID, "%d pieces: 1 .. %u", np, stage_maxp(c));
     const bool wfield = KW == 1 && 2 * k <= WKEY_MAX_BITS;
@@ -3332,16 +3194,14 @@ FK_EXPORT int fk_debug_count_pieces(fk_ctx *c, int32_t F, int32_t np, const uint
     const StreamWs on = c->main_on();
     hipStream_t s = on.s;
     HIP_TRY(hipStreamSynchronize(s));
-    // a new job without input: what map_records resets
-    reset_results(c);
-    c->stats = fk_stats{};
-    c->nrec = 0;
-    c->rec_tiled = false;
-    pieces_reset(c);
+    // pieces without an input (no job is open, see above): a new result over staged pieces of their own;
+    // the last input and what fk_map or fk_debug_fastq_ms would read of its job stay
+    end_pieces(c);
+    new_result(c);
     c->nkmers = sumw;
     c->stats.kmers = sumw;
-    c->st_plan = sorted_plan(c, entries, F);
-    if (!c->st_plan.tiered || !c->st_plan.two_level) return set_err(FK_E_STATE, "staged pieces need the tiered two-level count");
+    c->job.st_plan = sorted_plan(c, entries, F);
+    if (!c->job.st_plan.tiered || !c->job.st_plan.two_level) return set_err(FK_E_STATE, "staged pieces need the tiered two-level count");
     uint64_t maxp = 0;
     for (int p = 0; p < np; ++p) {
         const uint64_t n = cb[p][ncell_all];
@@ -3353,22 +3213,28 @@ FK_EXPORT int fk_debug_count_pieces(fk_ctx *c, int32_t F, int32_t np, const uint
     }
     FK_TRY(ensure(c->st_total, ncell_all * 8));
     HIP_TRY(hipMemcpy(c->st_total.p, total.data(), ncell_all * 8, hipMemcpyHostToDevice));
-    c->st_np = (uint32_t)np;
-    c->st_kmers = entries;
-    c->st_weighted = weighted != 0;
+    c->job.st_np = (uint32_t)np;
+    c->job.st_kmers = entries;
+    c->job.st_weighted = weighted != 0;
     int rc = FK_OK;
     if (fold_mask) rc = ensure(c->mid, maxp * 8);  // the fold's scratch: in a job, the piece's first expansion level
     for (int p = 0; p < np && rc == FK_OK; ++p)
         if (fold_mask >> p & 1u) rc = fold_piece(c, on, (uint32_t)p, cb[p][ncell_all]);
     if (rc == FK_OK) rc = staged_count(c, nullptr);
     if (rc == FK_OK) fold_report(c, true);
-    pieces_reset(c);
+    end_pieces(c);
     return rc;
 }
 
 FK_EXPORT int fk_debug_tier_stats(const fk_ctx *c, uint64_t out[8]) {
     if (!c || !out) return set_err(FK_E_INVALID, "null argument");
     std::copy(c->tier_last, c->tier_last + 8, out);
+    return FK_OK;
+}
+
+FK_EXPORT int fk_debug_live_resources(uint64_t out[4]) {
+    if (!out) return set_err(FK_E_INVALID, "null argument");
+    for (int i = 0; i < 4; ++i) out[i] = g_live[i].load(std::memory_order_relaxed);
     return FK_OK;
 }
 
@@ -3419,7 +3285,7 @@ FK_EXPORT int fk_signature_counts(fk_ctx *c, void *d_counts, uint64_t n_counts) 
     if (n_counts < slots)
         return set_err(FK_E_RANGE, "signature counts hold %llu entries, need 4^m + 1 = %llu",
                        (unsigned long long)n_counts, (unsigned long long)slots);
-    if (c->pm_active && !c->pm_last_seen)
+    if (c->job.pm_active && !c->job.pm_last_seen)
         return set_err(FK_E_STATE, "fk_signature_counts inside a streamed input: finish it with fk_ingest(..., last = 1)");
     hipStream_t s = c->stream;
     const uint64_t n = c->d_fasta ? c->n_fasta : 0;
@@ -3470,7 +3336,7 @@ FK_EXPORT int fk_write_bin_signatures(fk_ctx *c, const void *d_counts, uint64_t 
                        (unsigned long long)n_counts, (unsigned long long)slots);
     hipStream_t s = c->stream;
     const unsigned long long *counts = (const unsigned long long *)d_counts;
-    TempBuf nz, pairs;
+    DevBuf nz, pairs;
     FK_TRY(ensure(nz, 8));
     unsigned long long nnz = 0;
     HIP_TRY(hipMemsetAsync(nz.p, 0, 8, s));
@@ -3527,7 +3393,7 @@ FK_EXPORT int fk_find_bin_signatures(fk_ctx *c, const char *out_dir) {
     if (!c || !out_dir) return set_err(FK_E_INVALID, "null argument");
     DeviceGuard dg_(c->device);
     const uint64_t slots = fk_signature_slots(c);
-    TempBuf counts;
+    DevBuf counts;
     FK_TRY(ensure(counts, slots * 8));
     FK_TRY(fk_signature_counts(c, counts.p, slots));
     return fk_write_bin_signatures(c, counts.p, slots, out_dir);

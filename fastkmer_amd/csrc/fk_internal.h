@@ -15,6 +15,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <utility>
+
 #include "fk_common.h"
 
 namespace fk {
@@ -76,10 +78,20 @@ struct Chunk {
     uint32_t lbin, pad;
 };
 
-// Grow-only scratch space for the scans.
+// Grow-only scratch space for the scans: the scans grow it (fk_kernels.hip), its holder frees it once the
+// streams that scanned with it have drained.  Move-only.
 struct ScanWorkspace {
     void *ptr = nullptr;
     size_t bytes = 0;
+    ScanWorkspace() = default;
+    ScanWorkspace(ScanWorkspace &&o) noexcept : ptr(o.ptr), bytes(o.bytes) { o.ptr = nullptr, o.bytes = 0; }
+    ScanWorkspace &operator=(ScanWorkspace &&o) noexcept {
+        std::swap(ptr, o.ptr), std::swap(bytes, o.bytes);
+        return *this;
+    }
+    ~ScanWorkspace() {
+        if (ptr) (void)hipFree(ptr);
+    }
 };
 
 // ---- scans (exclusive); `total` (device, may be null) receives the sum/max

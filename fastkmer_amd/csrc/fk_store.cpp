@@ -21,17 +21,13 @@ double wall_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-// A call's own events, destroyed when its scope ends.
+// A call's own timed events.
 template <int N>
 struct Events {
-    hipEvent_t e[N] = {};
+    Event e[N];
     int create() {
-        for (int i = 0; i < N; ++i) HIP_TRY(hipEventCreate(&e[i]));
+        for (int i = 0; i < N; ++i) HIP_TRY(e[i].create());
         return FK_OK;
-    }
-    ~Events() {
-        for (int i = 0; i < N; ++i)
-            if (e[i]) (void)hipEventDestroy(e[i]);
     }
     double ms(int a, int b) const {
         float t = 0.f;
@@ -95,7 +91,7 @@ const char *why_text(uint32_t why) {
 // local bins by bin_sizes (all Bc bins).
 int import_layout(fk_ctx *c, const uint64_t *bin_sizes, std::vector<uint64_t> &off) {
     if (c->cfg.use_ht) return set_err(FK_E_INVALID, "%s", MSG_NEED_SORTED);
-    if (c->job_open || c->dev_open || c->xch.open)
+    if (c->job.job_open || c->job.dev_open || c->job.xch.open)
         return set_err(FK_E_STATE, "an import inside a job (between its first fk_ingest and fk_finish)");
     reset_results(c);
     std::vector<uint64_t> per(c->nlb, 0);
@@ -315,7 +311,7 @@ FK_EXPORT int fk_export(fk_ctx *c, uint64_t *keys, uint32_t *counts, size_t cap,
     if (cap < D) return set_err(FK_E_RANGE, "the result has %llu k-mers, the buffers hold %zu", (unsigned long long)D, cap);
     if (D == 0) return FK_OK;
     if (!keys || !counts) return set_err(FK_E_INVALID, "null argument");
-    TempBuf dk, dc;
+    DevBuf dk, dc;
     FK_TRY(ensure(dk, D * 8 * c->KW));
     FK_TRY(ensure(dc, D * 4));
     FK_TRY(export_queue(c, dk.as<uint64_t>(), dc.as<uint32_t>()));
@@ -367,7 +363,7 @@ FK_EXPORT int fk_save(fk_ctx *c, const char *path) {
     Events<4> ev;
     FK_TRY(ev.create());
     // the result dense in the file's order, and its checksum
-    TempBuf dk, dc, pk, pc, res;
+    DevBuf dk, dc, pk, pc, res;
     FK_TRY(ensure(dk, D * kb));
     FK_TRY(ensure(dc, D * 4));
     FK_TRY(ensure(res, 64));
@@ -481,7 +477,7 @@ FK_EXPORT int fk_load(fk_ctx *c, const char *path) {
     FK_TRY(ensure(c->out_keys, D * kb));
     FK_TRY(ensure(c->out_counts, D * 4));
     // the sections land in the context's arrays, or (another order) in temporaries permuted into them
-    TempBuf tk, tc;
+    DevBuf tk, tc;
     uint64_t *fkeys = c->out_keys.as<uint64_t>();
     uint32_t *fcounts = c->out_counts.as<uint32_t>();
     if (!same) {
@@ -525,7 +521,7 @@ FK_EXPORT int fk_load(fk_ctx *c, const char *path) {
                      (unsigned long long)h.kmers, (unsigned long long)sums[1]);
     if (rc == FK_OK && !same) {
         // the checksum is over the file's order: once more over the sections as they were stored
-        TempBuf res;
+        DevBuf res;
         uint64_t fs[4] = {0, 0, 0, 0};
         rc = ensure(res, 64);
         if (rc == FK_OK) {

@@ -1,7 +1,7 @@
 // fk_views.cpp -- the C-ABI calls that only read a finished result (include/fastkmer.h): bins, lookups,
 // bin files, the spectrum, filtered bins, the two-sample comparison, per-read profiles.  The result is the
 // context's (fk_ctx.h), left bucket-major by the count in fk_api.cpp.  The calls stage through the
-// context's grow-only ViewBufs; what spans the whole result is a call's own TempBuf.
+// context's grow-only ViewBufs; what spans the whole result is a call's own DevBuf.
 #include <errno.h>
 #include <stdio.h>
 #include <string.h>
@@ -222,7 +222,7 @@ static int write_bin_text(fk_ctx *c, const char *out_dir, const uint64_t *keys, 
     const uint32_t nlb = c->nlb;
     const int eof = c->cfg.use_ht == 0;
     if (D == 0) return FK_OK;  // no k-mers: no bin files
-    TempBuf len, off, bbytes, text;
+    DevBuf len, off, bbytes, text;
     FK_TRY(ensure(len, D * 4));
     FK_TRY(ensure(off, (D + 1) * 8));
     FK_TRY(ensure(bbytes, ((uint64_t)nlb + 1) * 8));
@@ -235,16 +235,14 @@ static int write_bin_text(fk_ctx *c, const char *out_dir, const uint64_t *keys, 
     const uint64_t T = bb[nlb];
     FK_TRY(ensure(text, T + 16));
     HIP_TRY(launch_format_lines(c->KW, keys, counts, D, c->cfg.k, off.as<uint64_t>(), text.as<uint8_t>(), s));
-    uint8_t *host = nullptr;
+    PinBuf pin;
     if (T) {
-        HIP_TRY(hipHostMalloc((void **)&host, T, hipHostMallocDefault));
-        const hipError_t e = hipMemcpyAsync(host, text.p, T, hipMemcpyDeviceToHost, s);
+        HIP_TRY(pin.alloc(T, hipHostMallocDefault));
+        const hipError_t e = hipMemcpyAsync(pin.p, text.p, T, hipMemcpyDeviceToHost, s);
         const hipError_t e2 = e == hipSuccess ? hipStreamSynchronize(s) : e;
-        if (e2 != hipSuccess) {
-            (void)hipHostFree(host);
-            return set_err(FK_E_DEVICE, "copying the bin text to the host: %s", hipGetErrorString(e2));
-        }
+        if (e2 != hipSuccess) return set_err(FK_E_DEVICE, "copying the bin text to the host: %s", hipGetErrorString(e2));
     }
+    const uint8_t *host = pin.as<uint8_t>();
     const std::string dir(out_dir);
     const unsigned nth = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
     std::vector<int> errs(nth, 0);
@@ -262,7 +260,6 @@ static int write_bin_text(fk_ctx *c, const char *out_dir, const uint64_t *keys, 
         });
     }
     for (auto &x : th) x.join();
-    if (host) (void)hipHostFree(host);
     for (int e : errs)
         if (e) return set_err(FK_E_IO, "writing bin files under %s failed", out_dir);
     return FK_OK;
@@ -495,7 +492,7 @@ static int filtered_offsets(fk_ctx *c, Filter &f, DevBuf &kept, DevBuf &off, Dev
 static int filtered_bin_sizes(fk_ctx *c, Filter f, uint64_t *out) {
     for (int32_t b = 0; b < c->Bc; ++b) out[b] = 0;
     if (c->distinct == 0) return FK_OK;
-    TempBuf kept, off, d_off;
+    DevBuf kept, off, d_off;
     std::vector<uint64_t> h_off;
     FK_TRY(filtered_offsets(c, f, kept, off, d_off, h_off));
     owned_bin_sizes(c, h_off, out);
@@ -573,7 +570,7 @@ FK_EXPORT int fk_write_bins_range(fk_ctx *c, const char *out_dir, uint32_t min_c
     if (mkdir_p(out_dir) != 0) return set_err(FK_E_IO, "cannot create %s: %s", out_dir, strerror(errno));
     if (c->distinct == 0) return FK_OK;  // no k-mers: no bin files
     Filter f{min_count, max_count};
-    TempBuf kept, off, d_off, fkeys, fcounts;
+    DevBuf kept, off, d_off, fkeys, fcounts;
     std::vector<uint64_t> h_off;
     FK_TRY(filtered_offsets(c, f, kept, off, d_off, h_off));
     const uint64_t D = h_off[c->nlb];

@@ -685,6 +685,10 @@ int fk_debug_tier_stats(const fk_ctx *ctx, uint64_t out[8]);
  * out_cb = the exclusive scan of its keys per cell, (bins << F) + 1 words, the last
  * one the piece's keys; out_keys (or NULL) = those keys.  Valid until the next job. */
 int fk_debug_staged_piece(fk_ctx *ctx, int32_t p, uint64_t *out_keys, uint64_t *out_cb);
+/* Device allocations, pinned host allocations, events and streams currently owned by the library's
+ * contexts and calls in this process (a communicator's own are not included, nor a scan workspace --
+ * at most two device allocations per context, made inside the scans).  Test hook. */
+int fk_debug_live_resources(uint64_t out[4]);
 
 /* ---- test hooks of the failure semantics (no reference counterpart) ----
  * fk_debug_comm_hold queues, on every stream the context's collectives run on,
