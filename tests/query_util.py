@@ -83,8 +83,8 @@ class OracleTable:
     def __len__(self):
         return len(self.lo)
 
-    def expected(self, qhi, qlo, k):
-        """The oracle's count of every query key (either strand): 0 for a k-mer it does not hold."""
+    def find(self, qhi, qlo, k):
+        """The index in the table of every query key (either strand), -1 for a k-mer it does not hold."""
         chi, clo = canonical(qhi, qlo, k)
         n = len(self)
         hi, lo = np.concatenate([self.hi, chi]), np.concatenate([self.lo, clo])
@@ -94,9 +94,15 @@ class OracleTable:
         new[1:] = (sh[1:] != sh[:-1]) | (sl[1:] != sl[:-1])
         gid = np.empty(len(order), dtype=np.int64)
         gid[order] = np.cumsum(new) - 1
-        table = np.zeros(int(gid.max()) + 1 if len(gid) else 0, dtype=np.uint32)
-        table[gid[:n]] = self.count
-        return table[gid[n:]]
+        at = np.full(int(gid.max()) + 1 if len(gid) else 0, -1, dtype=np.int64)
+        at[gid[:n]] = np.arange(n)
+        return at[gid[n:]]
+
+    def expected(self, qhi, qlo, k):
+        """The oracle's count of every query key (either strand): 0 for a k-mer it does not hold."""
+        at = self.find(qhi, qlo, k)
+        table = np.concatenate([self.count, np.zeros(1, dtype=np.uint32)])  # index -1: absent
+        return table[at]
 
 
 def kmer_bins(keys, k, m, B):

@@ -37,13 +37,22 @@ class Pair:
     """Two inputs with the oracle's results over them and (ca, cb) of every k-mer of their union."""
 
     def __init__(self, fa, fb, k, m, B, tab_a=None, threads=1):
-        self.fasta, self.k, self.m, self.B = (fa, fb), k, m, B
         if tab_a is None:
             ra = oracle.OracleResult(fa, k, m, B, threads=threads)
             tab_a = OracleTable(ra, ra.nbins)
         rb = oracle.OracleResult(fb, k, m, B, threads=threads)
-        self.nbins = rb.nbins
-        self.tabs = (tab_a, OracleTable(rb, rb.nbins))
+        self._join((fa, fb), k, m, B, rb.nbins, tab_a, OracleTable(rb, rb.nbins))
+
+    @classmethod
+    def of_tables(cls, tab_a, tab_b, k, m, B, nbins):
+        """A pair over two tables made elsewhere (query_util.OracleTable's fields), without inputs."""
+        self = cls.__new__(cls)
+        self._join(None, k, m, B, nbins, tab_a, tab_b)
+        return self
+
+    def _join(self, fasta, k, m, B, nbins, tab_a, tab_b):
+        self.fasta, self.k, self.m, self.B, self.nbins = fasta, k, m, B, nbins
+        self.tabs = (tab_a, tab_b)
         na = len(tab_a)
         hi = np.concatenate([t.hi for t in self.tabs])
         lo = np.concatenate([t.lo for t in self.tabs])
